@@ -1,7 +1,11 @@
 """bench.py - headline benchmark of the hot path (BASELINE.json metric) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus 1 --steps K --warmup W --full   (+ call-by-call step, per-kernel-class roofline, GEMM / MFMA-loop
+                                                            cross-check, 256^3 / 512^3 prediction and merge, CPU baselines)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy)
 
+A plain run sets up, warms up, times K steps and prints the headline line; everything else it measures is behind --full.
 A step = one training step of U-Net/ResNet-34 (2 classes) on a batch of 32 synthetic 256x256 slices that
 are already resident in HBM: weight-copy refresh, forward (train-mode BN), DiceLoss(normalization="none"),
 backward (all weights trainable), gradient all-reduce over RCCL when N > 1, fused AdamW, OneCycleLR step -
@@ -11,6 +15,7 @@ fp32 master weights.  Prints ONE JSON line on rank 0.
 from __future__ import annotations
 
 import argparse
+import copy
 import json
 import os
 import sys
@@ -115,6 +120,33 @@ def dice_loss(output, target, eps=1e-6):
     inter = (output * target).sum((0, 2, 3))
     denom = (output * output).sum((0, 2, 3)) + (target * target).sum((0, 2, 3))
     return 1.0 - torch.mean(2 * (inter / denom.clamp(min=eps)))
+
+
+DUMP_MAX_ELEMS = 1 << 21     # per array: 8 MB of float32, the dump stays far below 64 MB
+
+
+def dump_outputs(out_dir: str, model, loss) -> dict:
+    """What a caller of the timed step holds after its last call, as out_dir/<name>.npy: the loss it returned (float64), the
+    fp32 master parameters it updated, their gradients and the BatchNorm running statistics (float32).  A tensor of more than
+    DUMP_MAX_ELEMS elements is written as a seeded sample of its flat positions - the same positions on every run of the same
+    configuration (the ResNet-34 U-Net's 24 M parameters would be 98 MB per array)."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+
+    def sample(t, seed):
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(seed).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.float().cpu().numpy()
+
+    arrays = {"loss": np.array([float(loss.detach())], dtype=np.float64),
+              "params": sample(model._flat, 1),
+              "grads": sample(model._flat_grad, 1),
+              "bn_running_stats": sample(model._bnstate, 2)}
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def rank_is_zero() -> bool:
@@ -410,6 +442,13 @@ def main():
     ap.add_argument("--size", type=int, default=256, help="slice height = width")
     ap.add_argument("--classes", type=int, default=2)
     ap.add_argument("--per-unit", default="", help="write a per-layer kernel-time table (instrumented steps) to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure the rest: the step call by call, per-kernel-class timing and "
+                         "rooflines from instrumented steps, the library GEMM / MFMA-loop cross-check, the 256^3 and 512^3 "
+                         "prediction and merge legs (unless --no-predict) and the CPU baselines (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (loss, updated parameters, gradients, BatchNorm "
+                         "running statistics; large tensors as a fixed seeded sample) as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -482,6 +521,11 @@ def main():
     for _ in range(setup_steps):
         step()
     torch.cuda.synchronize()
+    # the state after the set-up steps, put back before the warm-up: how many burst steps run below depends on timing, and the
+    # steps timed (and --dump-outputs) must start from the same parameters, optimiser state and schedule position on every run
+    tracked = (model._flat, model._bnstate, model._nbt, opt.exp_avg, opt.exp_avg_sq)
+    snap = ([t.clone() for t in tracked], opt.step_count, {k: v for k, v in opt.param_groups[0].items() if k != "params"},
+            copy.deepcopy(sched.state_dict()))
     graph_mode = bool(use_graph and model._steps and all(g is not None for st in model._steps.values() for g in st["graphs"].values()))
     # Untimed set-up, continued: bursts of `steps` back-to-back steps (the shape of the timed region) until two consecutive
     # bursts agree within 2 %.  A process's first bursts run 1.5-2.5x slower than its steady state (measured:
@@ -489,7 +533,10 @@ def main():
     # second of earlier activity brings the first burst to 7.0, 1.5 s to 5.0): a training run leaves that transient behind in
     # its first second, a 20-step timed region would consist of nothing else.  The same bursts rank the two step modes on this
     # box: replayed graphs cost the host ~0.4 ms per step against ~2 ms call by call, but order the two streams range by range
-    # instead of unit by unit (~2 % more GPU time).
+    # instead of unit by unit (~2 % more GPU time).  A burst is at most 100 steps long, so that the set-up stays a few seconds
+    # however many steps are timed.
+    burst_steps = max(4, min(args.steps, 100))
+
     def burst(fn, k):
         fn(); torch.cuda.synchronize()
         t = time.perf_counter()
@@ -504,7 +551,7 @@ def main():
     hist = {nm: [] for nm, _ in modes}
     for i in range(12):
         for nm, fn in modes:
-            hist[nm].append(round(burst(fn, max(4, args.steps)), 4))
+            hist[nm].append(round(burst(fn, burst_steps), 4))
         if world > 1:
             if i >= 3:      # a fixed count when ranks run collectives inside the steps: every rank must leave the loop together
                 break
@@ -519,6 +566,13 @@ def main():
             last = tt.tolist()
         use_graph = graph_mode = last[0] <= last[1]
         autotune["picked"] = "graph" if use_graph else "eager"
+    with torch.no_grad():
+        for t, saved in zip(tracked, snap[0]):
+            t.copy_(saved)
+    opt.step_count = snap[1]
+    opt.param_groups[0].update(snap[2])
+    sched.load_state_dict(snap[3])
+    del snap
     log(f"setup done (replaying recorded step graphs: {graph_mode} {autotune}); warming up")
     for _ in range(args.warmup):
         step()
@@ -542,9 +596,51 @@ def main():
         elapsed = tt.item()
     final_loss = float(loss.detach())
     log(f"timed region: {elapsed / args.steps * 1e3:.3f} ms/step (host enqueue {t_enq / args.steps * 1e3:.3f} ms/step)")
+    dumped = None
+    if rank == 0 and args.dump_outputs:     # before anything below runs another step on the model
+        dumped = dump_outputs(args.dump_outputs, model, loss)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
+
+    ms_per_step = elapsed / args.steps * 1e3
+    slices_per_s = args.batch * world * args.steps / elapsed
+    if rank == 0:
+        out = {
+            "metric": ("slices/sec fwd+bwd U-Net/ResNet-34 256x256 bf16 batch 32 (training step incl. loss, AdamW)" if headline else
+                       f"slices/sec fwd+bwd {args.topology}/{args.encoder} {args.size}x{args.size} {args.precision} batch {args.batch} "
+                       f"{args.classes}-class (training step incl. loss, AdamW) - NOT the headline configuration"),
+            "value": round(slices_per_s, 2), "unit": "slices/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.precision, "data": "synthetic",
+            "config": {"workload": ("configs[1]: synthetic 256^3-style 1-ch slices, 2-class, U-Net/ResNet-34, batch 32 per GPU, "
+                                    "train step (fwd + DiceLoss + bwd + AdamW + OneCycleLR)") if headline else
+                                   (f"synthetic 1-ch slices, {args.classes}-class, {args.topology}/{args.encoder}, batch {args.batch} per GPU, "
+                                    "train step (fwd + DiceLoss + bwd + AdamW + OneCycleLR)"),
+                       "global_batch": args.batch * world, "slice": f"{args.size}x{args.size}", "parallelism": f"dp{world}",
+                       "master_weights": "fp32", "final_loss": round(final_loss, 5),
+                       **({"grad_allreduce": str(model.dp_grad_dtype).replace("torch.", "") + " buckets inside backward"} if world > 1 else {})},
+            "whole_step_mfma_frac": round(slices_per_s / world * FLOP_PER_SLICE_FWD_BWD_256 / 1e12 / MFMA_PEAK_BF16_TFLOPS, 4) if headline else None,
+            "step_timing": {
+                "mode": "hipGraph replay (forward + DiceLoss + backward + AdamW recorded once per weight set as linear graphs "
+                        "per unit range and stream)" if graph_mode else "call by call",
+                "autotune_at_setup": autotune,
+                "setup_steps_untimed": setup_steps + sum(len(h) * (burst_steps + 1) for h in autotune["bursts_ms"].values()),
+                "host_enqueue_ms": round(t_enq / args.steps * 1e3, 4),
+                "note": "the timed steps start from the state after the first set-up steps, whatever the bursts in between ran.  "
+                        "The timed loop does not read the loss back (the reference's loop does, loss.item() at "
+                        "vol_seg_2d_trainer.py:220 - one sync per step)."},
+            **({"dumped_outputs": {"dir": args.dump_outputs, "shapes": dumped}} if dumped else {}),
+        }
+    if not (args.full or args.per_unit):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full (and --per-unit): everything beyond the headline figure ----
     # the same steps call by call (no graph): what the host costs when it enqueues ~430 launches per step itself
     eager = {}
-    if world == 1:
+    if world == 1 and args.full:
         n_e = 10
         for _ in range(2):
             step_eager()
@@ -587,7 +683,7 @@ def main():
     log("instrumented steps done")
 
     predict = {}
-    if not args.no_predict:
+    if args.full and not args.no_predict:
         del opt, sched
         model.release_plans()     # vs_graph_destroy / vs_unet_destroy for the training plans
         torch.cuda.empty_cache()
@@ -599,9 +695,7 @@ def main():
         if rank == 0:
             predict["merge_512cube"] = merge_bench(dev)
 
-    if rank == 0:
-        ms_per_step = elapsed / args.steps * 1e3
-        slices_per_s = args.batch * world * args.steps / elapsed
+    if rank == 0 and args.full:     # (--per-unit alone: the table is written, the line stays the plain one)
         mfma_kinds = ("conv_fwd", "conv_dgrad", "conv_wgrad")
         # dominant kernel symbol: forward and dgrad share conv_igemm_kernel<T,BN,PT,TAPS,STRIDE>; group its launches by instantiation
         byvar = {}
@@ -624,36 +718,15 @@ def main():
                          **({"tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2)} if v["flops"] and v["ms"] else {}),
                          **({"gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} if v["bytes"] and v["ms"] else {})}
                      for k, v in prof.items()}
-        out = {
-            "metric": ("slices/sec fwd+bwd U-Net/ResNet-34 256x256 bf16 batch 32 (training step incl. loss, AdamW)" if headline else
-                       f"slices/sec fwd+bwd {args.topology}/{args.encoder} {args.size}x{args.size} {args.precision} batch {args.batch} "
-                       f"{args.classes}-class (training step incl. loss, AdamW) - NOT the headline configuration"),
-            "value": round(slices_per_s, 2), "unit": "slices/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic",
-            "config": {"workload": ("configs[1]: synthetic 256^3-style 1-ch slices, 2-class, U-Net/ResNet-34, batch 32 per GPU, "
-                                    "train step (fwd + DiceLoss + bwd + AdamW + OneCycleLR)") if headline else
-                                   (f"synthetic 1-ch slices, {args.classes}-class, {args.topology}/{args.encoder}, batch {args.batch} per GPU, "
-                                    "train step (fwd + DiceLoss + bwd + AdamW + OneCycleLR)"),
-                       "global_batch": args.batch * world, "slice": f"{args.size}x{args.size}", "parallelism": f"dp{world}",
-                       "master_weights": "fp32", "final_loss": round(final_loss, 5),
-                       **({"grad_allreduce": str(model.dp_grad_dtype).replace("torch.", "") + " buckets inside backward"} if world > 1 else {})},
-            "whole_step_mfma_frac": round(slices_per_s / world * FLOP_PER_SLICE_FWD_BWD_256 / 1e12 / MFMA_PEAK_BF16_TFLOPS, 4) if headline else None,
-            # where a step's wall time goes: a host- or gap-bound run shows ms_per_step well above the kernel sums
-            "step_timing": {
-                "mode": "hipGraph replay (forward + DiceLoss + backward + AdamW recorded once per weight set as linear graphs "
-                        "per unit range and stream)" if graph_mode else "call by call",
-                "autotune_at_setup": autotune,
-                "setup_steps_untimed": setup_steps + sum(len(h) * (max(4, args.steps) + 1) for h in autotune["bursts_ms"].values()),
-                "host_enqueue_ms": round(t_enq / args.steps * 1e3, 4),
-                "main_stream_kernel_sum_ms": round(sum(v["ms"] for k, v in prof.items() if k != "conv_wgrad") / prof_steps, 4),
-                "side_stream_kernel_sum_ms": round(prof["conv_wgrad"]["ms"] / prof_steps, 4),
-                "gpu_kernel_sum_ms": round(sum(v["ms"] for v in prof.values()) / prof_steps, 4),
-                "call_by_call": eager,
-                "note": "kernel sums: HIP-event durations of 3 serialised instrumented steps (side stream off; AdamW and the "
-                        "weight-copy kernels, ~0.2 ms on the side stream, are not in the event classes); in the timed region the "
-                        "weight gradients overlap the caller's stream.  The timed loop does not read the loss back (the "
-                        "reference's loop does, loss.item() at vol_seg_2d_trainer.py:220 - one sync per step)."},
+        out["step_timing"].update({
+            "main_stream_kernel_sum_ms": round(sum(v["ms"] for k, v in prof.items() if k != "conv_wgrad") / prof_steps, 4),
+            "side_stream_kernel_sum_ms": round(prof["conv_wgrad"]["ms"] / prof_steps, 4),
+            "gpu_kernel_sum_ms": round(sum(v["ms"] for v in prof.values()) / prof_steps, 4),
+            "call_by_call": eager,
+            "note": "kernel sums: HIP-event durations of 3 serialised instrumented steps (side stream off; AdamW and the "
+                    "weight-copy kernels, ~0.2 ms on the side stream, are not in the event classes); in the timed region the "
+                    "weight gradients overlap the caller's stream.  " + out["step_timing"]["note"]})
+        out.update({
             "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": round(ach, 2), "peak": MFMA_PEAK_BF16_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(ach / MFMA_PEAK_BF16_TFLOPS, 4), "traffic": (load_traffic(dom_name) or {}).get("bytes_per_launch"), "traffic_detail": load_traffic(dom_name),
                          "launches_per_step": dom_calls // prof_steps,
@@ -664,7 +737,7 @@ def main():
                                  "3 serialised instrumented steps (side stream off); the timed region overlaps wgrad on a side stream"},
             "kernel_classes": breakdown,
             **predict,
-        }
+        })
         # the class with the largest time share next to the dominant forward / dgrad kernel (for the headline step: the weight
         # gradients), same definition: algorithmic FLOPs of its launches / sum of their HIP-event durations
         big = max(mfma_kinds, key=lambda k: prof[k]["ms"])
@@ -699,6 +772,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(12, args.cpu_steps)
             if not args.no_predict:
                 out["cpu_baseline_predict"] = cpu_baseline_predict()
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
