@@ -452,6 +452,67 @@ def test_normalise_on_load_plan_is_the_one_reader_rule():
                           "decoder.blocks.3.conv1.0.weight"]), dec
 
 
+def test_conv_plan_codes_and_stat_rows_of_the_headline_launches():
+    """conv_plan (host logic, nothing is launched) through vs_conv2d_train_variant / vs_conv2d_stat_rows: the kernel code (cout tile * 1000 +
+    pixel tiles * 100 + taps * 10 + kind) and the partial-statistics rows of the distinct bf16 convolution launches of the batch-32 256 x 256
+    U-Net / ResNet-34 step (forward with statistics bins, data gradients plain / zero-stuffed / pooled with a split output) and of a batch of
+    128 prediction slices of 512 x 512 - every family: tile (kinds 1, 2, 8), direct (4), ring (6), stream (7).  Recorded from the build before
+    launch and queries shared one plan: moving a launch to another kernel is a decision that shows up here."""
+    import ctypes as C
+
+    from volume_segmantics_amd import _lib as L
+
+    table = (   # n, h = w, c0, c1, up0, cout, k, stride, out_f32, split_c, training block, code, stat_rows
+    (32, 64, 64, 0, 0, 64, 3, 1, 0, 0, "stats_bins", 64298, 512),
+    (32, 64, 64, 0, 0, 128, 3, 2, 0, 0, "stats_bins", 64292, 256),
+    (32, 64, 64, 0, 0, 128, 1, 2, 0, 0, "stats_bins", 64112, 512),
+    (32, 32, 128, 0, 0, 128, 3, 1, 0, 0, "stats_bins", 64296, 128),
+    (32, 32, 128, 0, 0, 256, 3, 2, 0, 0, "stats_bins", 64192, 128),
+    (32, 32, 128, 0, 0, 256, 1, 2, 0, 0, "stats_bins", 64112, 128),
+    (32, 16, 256, 0, 0, 256, 3, 1, 0, 0, "stats_bins", 32296, 32),
+    (32, 16, 256, 0, 0, 512, 3, 2, 0, 0, "stats_bins", 32192, 32),
+    (32, 16, 256, 0, 0, 512, 1, 2, 0, 0, "stats_bins", 32112, 32),
+    (32, 8, 512, 0, 0, 512, 3, 1, 0, 0, "stats_bins", 32296, 16),
+    (32, 16, 512, 256, 1, 256, 3, 1, 0, 0, "stats_bins", 32296, 32),
+    (32, 32, 256, 128, 1, 128, 3, 1, 0, 0, "stats_bins", 64296, 128),
+    (32, 64, 128, 64, 1, 64, 3, 1, 0, 0, "stats_bins", 64296, 512),
+    (32, 128, 64, 64, 1, 32, 3, 1, 0, 0, "stats_bins", 32298, 2048),
+    (32, 128, 32, 0, 0, 32, 3, 1, 0, 0, "stats_bins", 32298, 2048),
+    (32, 256, 32, 0, 1, 16, 3, 1, 0, 0, "stats_bins", 16294, 4096),
+    (32, 256, 16, 0, 0, 16, 3, 1, 0, 0, "stats_bins", 16294, 4096),
+    (32, 256, 16, 0, 0, 2, 3, 1, 3, 0, "none", 16294, 4096),
+    (32, 64, 64, 0, 0, 64, 3, 1, 0, 0, "none", 64297, 512),
+    (32, 16, 256, 0, 0, 256, 3, 1, 0, 0, "none", 32296, 32),
+    (32, 8, 512, 0, 0, 512, 3, 1, 0, 0, "none", 32296, 16),
+    (32, 64, 128, 0, 2, 64, 3, 1, 0, 0, "none", 64296, 512),
+    (32, 64, 128, 0, 2, 64, 1, 1, 0, 0, "none", 64218, 512),
+    (32, 32, 256, 0, 2, 128, 3, 1, 0, 0, "none", 64296, 128),
+    (32, 16, 512, 0, 2, 256, 3, 1, 0, 0, "none", 32296, 32),
+    (32, 128, 32, 0, 0, 32, 3, 1, 0, 0, "none", 32298, 2048),
+    (32, 256, 16, 0, 0, 16, 3, 1, 0, 0, "none", 16294, 4096),
+    (32, 16, 256, 0, 0, 768, 3, 1, 0, 512, "pool0", 64296, 32),
+    (32, 32, 128, 0, 0, 384, 3, 1, 0, 256, "pool0", 64296, 128),
+    (32, 64, 64, 0, 0, 192, 3, 1, 0, 128, "pool0", 64298, 512),
+    (32, 128, 32, 0, 0, 128, 3, 1, 0, 64, "pool0", 64298, 2048),
+    (32, 256, 16, 0, 0, 32, 3, 1, 0, 0, "pool0", 32298, 8192),
+    (128, 128, 64, 0, 0, 64, 3, 1, 0, 0, "none", 64297, 8192),
+    (128, 32, 256, 0, 0, 256, 3, 1, 0, 0, "none", 64297, 512),
+    (128, 16, 512, 0, 0, 512, 3, 1, 0, 0, "none", 64297, 128),
+    (128, 32, 512, 256, 1, 256, 3, 1, 0, 0, "none", 64298, 512),
+    (128, 256, 64, 64, 1, 32, 3, 1, 0, 0, "none", 32297, 32768),
+    (128, 256, 32, 0, 0, 32, 3, 1, 0, 0, "none", 32298, 32768),
+    (128, 512, 16, 0, 0, 16, 3, 1, 0, 0, "none", 16294, 16384),
+    (128, 512, 16, 0, 0, 4, 3, 1, 3, 0, "none", 16294, 16384),
+    )
+    assert len(table) <= 40
+    blocks = {"none": L.ConvTrain(), "stats_bins": L.ConvTrain(stats_bins=16, stats_nb=8), "pool0": L.ConvTrain(pool0=1)}   # (pointers are never dereferenced)
+    for n, hw, c0, c1, up0, cout, k, stride, out_f32, split_c, block, code, stat_rows in table:
+        d = L.ConvDesc(dtype=L.VS_BF16, n=n, hin=hw, win=hw, c0=c0, c1=c1, up0=up0, cout=cout, kh=k, kw=k, stride=stride, pad=k // 2,
+                       out_f32=out_f32, split_c=split_c, dilation=1)
+        got = L.lib.vs_conv2d_train_variant(C.byref(d), C.byref(blocks[block])), L.lib.vs_conv2d_stat_rows(C.byref(d), C.byref(blocks[block]))
+        assert got == (code, stat_rows), (n, hw, c0, c1, up0, cout, k, stride, out_f32, split_c, block, got)
+
+
 def test_sync_batchnorm_hook_is_accepted_only_where_it_is_built():
     """vs_unet_set_stats_hook (host logic): bf16 plans whose BatchNorms all sit behind bias-free convolutions / the ResNet stem take
     the cross-rank statistics hook (U-Net, U-Net++ / ResNet-50 = BASELINE configs[3], FPN); fp32 plans and networks with BatchNorm

@@ -49,6 +49,10 @@ extern "C" int vs_conv2d_fwd(const vs_conv_desc* d, const void* src0, const void
     return launch_conv_igemm(d->dtype, p, (hipStream_t)stream);
 }
 
+static void fake_pointers(const vs_conv_desc* d, ConvParams& p) {
+    p.src0 = (const void*)16; p.src1 = d->c1 ? (const void*)16 : nullptr; p.w = (const void*)16; p.out = (void*)16;
+    p.out1 = d->split_c > 0 ? (void*)16 : nullptr;
+}
 // which kernel instantiation vs_conv2d_fwd picks for this descriptor (with an affine epilogue where the descriptor allows one):
 // cout tile * 1000 + pixel tiles per wave * 100 + taps * 10 + kind (1 = stride-1 tile kernel, 2 = stride 2, 4 = direct shallow-layer
 // kernel, 6 = LDS-DMA ring, 7 = persistent LDS-DMA ring, 8 = 8-wave 256-pixel tiles); negative = error.  For tests and tools.
@@ -56,9 +60,8 @@ extern "C" int vs_conv2d_variant(const vs_conv_desc* d) {
     ConvParams p;
     int rc = desc_to_params(d, p);
     if (rc) return rc;
-    p.src0 = (const void*)16; p.src1 = d->c1 ? (const void*)16 : nullptr; p.w = (const void*)16; p.out = (void*)16;
-    p.out1 = d->split_c > 0 ? (void*)16 : nullptr;
-    return conv_igemm_variant(d->dtype, p);
+    fake_pointers(d, p);
+    return conv_plan(d->dtype, p).code;
 }
 
 // the training forms of the launch (statistics epilogue, pooled / masked data gradients, normalise on load): ConvParams as the
@@ -91,29 +94,26 @@ extern "C" int vs_conv2d_train(const vs_conv_desc* d, const void* src0, const vo
     VS_REQUIRE((d->c1 == 0) == (src1 == nullptr), "conv: src1 / c1 mismatch");
     VS_REQUIRE((d->split_c > 0) == (y1 != nullptr), "conv: y1 / split_c mismatch");
     p.src0 = src0; p.src1 = src1; p.w = w; p.residual = residual; p.out = y; p.out1 = y1;
-    if (p.pool0) VS_REQUIRE(conv_igemm_can_pool(p), "conv_train: no pooled epilogue for this geometry");
+    const ConvPlan plan = conv_plan(d->dtype, p);
+    if (p.pool0) VS_REQUIRE(plan.can_pool, "conv_train: no pooled epilogue for this geometry");
     if (p.nl_bins) VS_REQUIRE(conv_igemm_nl_ok(d->dtype, p), "conv_train: no normalise-on-load form for this layer");
-    if (p.stats_bins) VS_REQUIRE(conv_igemm_bins_ok(d->dtype, p), "conv_train: this layer's kernel has no statistics bins");
-    return launch_conv_igemm(d->dtype, p, (hipStream_t)stream);
+    if (p.stats_bins) VS_REQUIRE(d->dtype == VS_BF16, "conv_train: this layer's kernel has no statistics bins");   // (every bf16 kernel has them)
+    return launch_conv_igemm(d->dtype, p, (hipStream_t)stream, &plan);
 }
 
-static void fake_pointers(const vs_conv_desc* d, ConvParams& p) {
-    p.src0 = (const void*)16; p.src1 = d->c1 ? (const void*)16 : nullptr; p.w = (const void*)16; p.out = (void*)16;
-    p.out1 = d->split_c > 0 ? (void*)16 : nullptr;
-}
 extern "C" int vs_conv2d_train_variant(const vs_conv_desc* d, const vs_conv_train* t) {
     ConvParams p;
     int rc = train_to_params(d, t, p);
     if (rc) return rc;
     fake_pointers(d, p);
-    return conv_igemm_variant(d->dtype, p);
+    return conv_plan(d->dtype, p).code;
 }
 extern "C" int vs_conv2d_stat_rows(const vs_conv_desc* d, const vs_conv_train* t) {
     ConvParams p;
     int rc = train_to_params(d, t, p);
     if (rc) return rc;
     fake_pointers(d, p);
-    return conv_igemm_stat_rows(d->dtype, p);
+    return conv_plan(d->dtype, p).stat_rows;
 }
 extern "C" double vs_stat_scale(int which) { return which == 0 ? kStatScale1 : kStatScale2; }
 
@@ -204,7 +204,6 @@ extern "C" int vs_head_wgrad_planes(int dtype, const void* x, const float* dlogi
     return launch_conv_wgrad(dtype, p, (hipStream_t)stream);
 }
 
-int launch_weight_prepare(int dtype, const float* w, void* wc, void* wt, int cout, int taps, int cin, int cout_pad, hipStream_t s);
 /* fp32 [cout][taps][cin] -> dtype copy (wc, may be null) and flipped/transposed dgrad copy [cin][taps][cout] (wt) */
 extern "C" int vs_weights_prepare(int dtype, const float* w, void* wc, void* wt, int cout, int taps, int cin, void* stream) {
     VS_REQUIRE(w && (wc || wt), "weights_prepare: null pointer");

@@ -214,7 +214,8 @@ struct ConvParams {
     const float* scale; const float* shift;  // per-cout affine applied to the accumulator (may be null)
     const void* residual;                // same shape as out, added after the affine (may be null)
     int relu;
-    int out_f32;                         // store fp32 regardless of the compute dtype
+    int out_f32;                         // host side: bit 0 = store fp32 regardless of the compute dtype, bit 1 = NCHW layout; the kernels
+                                         // receive bit 0 alone (the layout bit travels in TileGeom / DirectGeom::out_nchw)
     int pool0;                           // dgrad through nearest-x2 upsampling: channels < (out1 ? split_c : Cout) are summed
                                          // over 2x2 pixel blocks and written to `out` at half resolution
     float* stats_partial;                // optional [tiles][2][Cout]: per-tile sum / sum of squares of the raw accumulators
@@ -259,19 +260,33 @@ struct VolScatter {
 // stage[n][hp][wp] packed keys -> cropped, max-merged into the key volume with the slice index as the fastest-moving lane
 // index: for directions whose slices are the volume's contiguous axis the head's own scatter would touch one line per voxel
 int launch_keys_stage_scatter(const uint32_t* stage, int nb, const vs_dirmap& m, int s0, uint32_t* keys, hipStream_t s);
-bool conv_head_scatter_ok(int dtype, const ConvParams& p);
-bool conv_igemm_bins_ok(int dtype, const ConvParams& p);     // whether p's kernel honours ConvParams::stats_bins   // whether launch_conv_igemm can honour p.scatter for this layer
+// Which kernel a convolution launch gets, decided once (conv_plan, conv_igemm.hip): the launch and every question about it
+// read the same plan.  p is taken as callers hold it: out_f32 packed (bit 0 = fp32 store, bit 1 = NCHW layout).
+// CONV_TILE: conv_igemm_kernel, register-staged tiles; CONV_DIRECT: conv_direct_kernel / conv_head_kernel, LDS-free strips of the shallow
+// layers; CONV_RING: conv_ring_kernel (conv_ring.h); CONV_STREAM: conv_stream_kernel (conv_stream.h), persistent
+enum ConvFamily { CONV_TILE, CONV_DIRECT, CONV_RING, CONV_STREAM };
+struct ConvPlan {
+    ConvFamily family;
+    int BN, PT, NW;      // the chosen kernel's cout tile, pixel tiles per wave, waves per workgroup
+    int ring;            // CONV_RING: 1 = 256-pixel tiles x 64 couts; 2 = 256-pixel tiles x 32 couts; 3 = pairs of 8 x 8 images x 32 couts
+    int stat_rows;       // partial rows stats_partial / bstats_partial receive (CONV_STREAM has no such epilogue: the rows of the
+                         // kernel that takes the launch once a statistics pointer is set)
+    bool can_pool;       // whether pool0 is supported for this geometry
+    int code;            // BN*1000 + PT*100 + taps*10 + kind (1 = stride-1 tile kernel, 2 = stride 2, 4 = direct, 6 = ring, 7 = stream,
+                         // 8 = 8-wave 256-pixel tiles): what the profiler and the tests read
+};
+ConvPlan conv_plan(int dtype, const ConvParams& p);
+// launches from `plan` - conv_plan(dtype, p) for p as it stands, the caller's promise - or decides for itself
+int launch_conv_igemm(int dtype, const ConvParams& p, hipStream_t s, const ConvPlan* plan = nullptr);
+// whether launch_conv_igemm can honour p.scatter for this layer
+inline bool conv_head_scatter_ok(const ConvParams& p, const ConvPlan& plan) { return p.scatter && plan.family == CONV_DIRECT; }
 bool conv_igemm_nl_ok(int dtype, const ConvParams& p);       // whether launch_conv_igemm can honour p.nl_* (normalise src0 on load)
-int launch_conv_igemm(int dtype, const ConvParams& p, hipStream_t s);
 // two chained evaluation-mode shallow layers (q reads p's output and nothing else does) as one launch: the tensor between them never exists
+bool conv_pair_ok(int dtype, const ConvParams& p, const ConvParams& q);
+int launch_conv_pair(int dtype, const ConvParams& p, const ConvParams& q, hipStream_t s);
 // the segmentation head's data gradient from dLoss / dlogits as fp32 NCHW planes (w: the forward's [classes][9][C] copy; out: [N][H][W][C])
 bool head_dgrad_planes_ok(int dtype, int classes, int H, int W, int C);
 int launch_head_dgrad_planes(int dtype, const float* dl, const void* w, void* out, int N, int classes, int H, int W, int C, hipStream_t s);
-bool conv_pair_ok(int dtype, const ConvParams& p, const ConvParams& q);
-int launch_conv_pair(int dtype, const ConvParams& p, const ConvParams& q, hipStream_t s);
-bool conv_igemm_can_pool(const ConvParams& p);      // whether pool0 is supported for this geometry
-int conv_igemm_stat_rows(int dtype, const ConvParams& p);   // number of partial rows stats_partial receives
-int conv_igemm_variant(int dtype, const ConvParams& p);      // BN*1000 + PT*100 + taps*10 + code of the chosen instantiation
 // Cross-rank BatchNorm statistics (SyncBatchNorm under data parallelism; vs_unet_set_stats_hook): `hook` sums `count` device values in
 // place over the ranks, stream-ordered on `stream` (kind 0: 64-bit integers - the fixed-point statistics bins, whose sum is exact and
 // the same bits on every rank; kind 1: fp32).  world = ranks contributing equal shares: the statistics then describe rows * world rows.
@@ -367,6 +382,14 @@ struct AdamwRanges { int n; long off[160]; long len[160]; };   // passed to the 
 int launch_adamw_slice(const vs_adamw_args& a, const float* grads, int64_t off, int64_t n, hipStream_t s);
 int launch_adamw_ranges(const vs_adamw_args& a, const float* grads, const AdamwRanges& r, hipStream_t s);
 int launch_weight_prepare(int dtype, const float* w, void* wc, void* wt, int cout, int taps, int cin, int cout_pad, hipStream_t s);
+// every layer's copies in one launch (per-layer HOST arrays of n entries), and the same behind the AdamW update of the weights
+int launch_weight_prepare_all(int dtype, const float* params, void* ws, int n, const long* w_off, const long* wc_off,
+                              const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad,
+                              const int* cg, hipStream_t s);
+int launch_adamw_prepare_all(int dtype, const vs_adamw_args& a, const float* grads, void* ws, int n, const long* w_off, const long* wc_off,
+                             const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad, const int* cg,
+                             const int* update, hipStream_t s);
+int launch_dlogits_to_nhwc16(int dtype, const float* d, void* o, int n, int k, int64_t hw, float* db, float* partial, hipStream_t s);
 // grouped convolution (cg channels per group, cin == cout): fp32 [cout][taps][cg] -> the block-expanded [cout][taps][32] copy
 // and its flipped / transposed twin [cin][taps reversed][32] (32-channel super-groups; zeros outside a group's own block)
 int launch_weight_prepare_grouped(int dtype, const float* w, void* wc, void* wt, int cout, int taps, int cg, hipStream_t s);

@@ -1018,25 +1018,6 @@ int launch_one(const ConvParams& p, const TileGeom& g, hipStream_t s) {
     return VS_OK;
 }
 
-template <typename T, int BN, int PT>
-int launch_tk(const ConvParams& p, const TileGeom& g, hipStream_t s) {
-    const int nt = p.KH * p.KW;
-    if constexpr (BN >= 32) {
-        if (p.dil == 2) return launch_one<T, BN, PT, 9, 1, 4, 2>(p, g, s);
-        if (p.dil == 4) return launch_one<T, BN, PT, 9, 1, 4, 4>(p, g, s);
-    }
-    if constexpr (PT == 1) {
-        if (p.stride == 2) return nt == 9 ? launch_one<T, BN, 1, 9, 2>(p, g, s) : launch_one<T, BN, 1, 1, 2>(p, g, s);
-    }
-    if constexpr (PT == 2 && BN == 64) {   // 8 x 16 output tiles of the stride-2 3x3 layers of a big batch
-        if (p.stride == 2) return launch_one<T, 64, 2, 9, 2>(p, g, s);
-    }
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        if (p.nl_bins) return launch_one<T, BN, PT, 9, 1, 4, 1, true>(p, g, s);     // (dispatch checked: stride-1 3x3, no dilation)
-    }
-    return nt == 9 ? launch_one<T, BN, PT, 9, 1>(p, g, s) : launch_one<T, BN, PT, 1, 1>(p, g, s);
-}
-
 struct Pick { int BN, PT, NW; };
 // tile width: static per kernel for stride 1 (see conv_igemm_kernel), by output width for stride 2
 static int tile_tw(const ConvParams& p, int PT) { return p.stride == 1 ? (PT == 1 ? 8 : 16) : (p.Wout >= 16 ? 16 : 8); }
@@ -1105,10 +1086,41 @@ static int ring_mode(int dtype, const ConvParams& p, int out_nchw) {
     return 0;
 }
 
+// The tile family's instantiations, looked up from the full tuple: a tuple that is not listed has no kernel (it never runs a neighbour's).
+constexpr int tile_key(int BN, int PT, int NW, int taps, int stride, int dil, bool nload) {
+    return (((((BN * 4 + PT) * 16 + NW) * 16 + taps) * 4 + stride) * 8 + dil) * 2 + (nload ? 1 : 0);
+}
 template <typename T>
-int dispatch(const ConvParams& p, int out_nchw, hipStream_t s) {
+int launch_tile(const ConvParams& p, const ConvPlan& plan, const TileGeom& g, hipStream_t s) {
+    constexpr bool kBf16 = std::is_same<T, bf16_t>::value;      // normalise-on-load is built for bf16 alone
+#define VS_TILE(bn, pt, nw, taps, stride, dil, nload)                                                        \
+    case tile_key(bn, pt, nw, taps, stride, dil, nload):                                                     \
+        if constexpr (!nload || kBf16) return launch_one<T, bn, pt, taps, stride, nw, dil, nload>(p, g, s);  \
+        break;
+#define VS_TILE_32UP(...) VS_TILE(64, __VA_ARGS__) VS_TILE(32, __VA_ARGS__)
+#define VS_TILE_BN(...) VS_TILE_32UP(__VA_ARGS__) VS_TILE(16, __VA_ARGS__)
+    switch (tile_key(plan.BN, plan.PT, plan.NW, p.KH * p.KW, p.stride, p.dil > 1 ? p.dil : 1, p.nl_bins != nullptr)) {
+        //      PT NW taps stride dil nload
+        VS_TILE_BN(2, 4, 9, 1, 1, false) VS_TILE_BN(2, 4, 1, 1, 1, false)       // 128-pixel tiles
+        VS_TILE_BN(1, 4, 9, 1, 1, false) VS_TILE_BN(1, 4, 1, 1, 1, false)       // 64-pixel tiles
+        VS_TILE_BN(2, 8, 9, 1, 1, false) VS_TILE_BN(2, 8, 1, 1, 1, false)       // 8 waves: 256-pixel tiles
+        VS_TILE_BN(1, 4, 9, 2, 1, false) VS_TILE_BN(1, 4, 1, 2, 1, false)       // stride 2
+        VS_TILE(64, 2, 4, 9, 2, 1, false)                                       // 8 x 16 output tiles of the stride-2 3x3 layers of a big batch
+        VS_TILE_32UP(2, 4, 9, 1, 2, false) VS_TILE_32UP(1, 4, 9, 1, 2, false)   // dilation 2: cout tiles of 32 and 64 only
+        VS_TILE_32UP(2, 4, 9, 1, 4, false) VS_TILE_32UP(1, 4, 9, 1, 4, false)   // dilation 4
+        VS_TILE_BN(2, 4, 9, 1, 1, true) VS_TILE_BN(1, 4, 9, 1, 1, true) VS_TILE_BN(2, 8, 9, 1, 1, true)   // normalise-on-load
+    }
+#undef VS_TILE_BN
+#undef VS_TILE_32UP
+#undef VS_TILE
+    vs_set_error("conv_igemm: no kernel for BN=%d PT=%d NW=%d", plan.BN, plan.PT, plan.NW);
+    return VS_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int dispatch(const ConvParams& p, const ConvPlan& plan, hipStream_t s) {
     constexpr int CK = CT<T>::CK, EPS = CT<T>::EPS;
-    const int Cin = p.C0 + p.C1;
+    const int Cin = p.C0 + p.C1, out_nchw = p.out_f32 >> 1;
     VS_REQUIRE(Cin % EPS == 0 && p.C0 % EPS == 0, "conv_igemm: channel counts must be multiples of %d", EPS);
     VS_REQUIRE(p.C1 == 0 || p.C0 % CK == 0, "conv_igemm: concat boundary must be a multiple of %d", CK);
     VS_REQUIRE(p.up0 >= 0 && p.up0 <= 2, "conv_igemm: up0 must be 0, 1 or 2");
@@ -1124,49 +1136,48 @@ int dispatch(const ConvParams& p, int out_nchw, hipStream_t s) {
     VS_REQUIRE(p.gc == 0 || (p.gc == 32 && p.C1 == 0 && p.C0 == p.Cout && p.Cout % 32 == 0 && !p.out1),
                "conv_igemm: grouped convolutions run on 32-channel super-groups with as many inputs as outputs");
     VS_REQUIRE(!(out_nchw || (p.Cout & 3)) || (!p.out1), "conv_igemm: ragged / NCHW output cannot be split");
-    const Pick cfg = pick_cfg(p);
-    const int BN = cfg.BN, PT = cfg.PT, NW = cfg.NW;
+    const int BN = plan.BN, PT = plan.PT, NW = plan.NW;
     if (p.out1) VS_REQUIRE(p.split_c % BN == 0, "conv_igemm: split_c %d not a multiple of the cout tile %d", p.split_c, BN);
     if (p.bz) {
-        VS_REQUIRE(!p.pool0 && !p.out1 && !p.scale && !p.shift && !p.relu && !p.out_f32 && !out_nchw && !(p.Cout & 3) && !p.stats_partial &&
+        VS_REQUIRE(!p.pool0 && !p.out1 && !p.scale && !p.shift && !p.relu && !p.out_f32 && !(p.Cout & 3) && !p.stats_partial &&
                    p.bmean && p.binvstd && p.bstats_partial && (!p.brelu || p.by || (p.bgamma && p.bbeta)),
                    "conv_igemm: the BN-backward epilogue takes a plain NHWC dgrad output");
     }
     if (p.pool0) {
-        VS_REQUIRE(PT >= 2 && p.Wout >= 16 && !(p.Hout & 1) && !(p.Wout & 1) && !p.residual && !p.scale && !p.shift && !out_nchw,
+        VS_REQUIRE(plan.can_pool && !p.residual && !p.scale && !p.shift && !out_nchw,
                    "conv_igemm: pooled dgrad epilogue not available for this geometry");
         VS_REQUIRE((p.out1 ? p.split_c : p.Cout) % 4 == 0, "conv_igemm: pooled channel count must be a multiple of 4");
     }
-    ConvParams pd = p;
-    pd.out_f32 = p.out_f32 | (out_nchw << 1);
     if (p.nl_bins) {
-        VS_REQUIRE(conv_igemm_nl_ok(Elem<T>::kDtype, pd) && p.nl_mean && p.nl_invstd && p.nl_gamma && p.nl_beta && p.nl_nb >= 1 && p.nl_rows >= 1,
+        VS_REQUIRE(conv_igemm_nl_ok(Elem<T>::kDtype, p) && p.nl_mean && p.nl_invstd && p.nl_gamma && p.nl_beta && p.nl_nb >= 1 && p.nl_rows >= 1,
                    "conv_igemm: normalise-on-load is built for the bf16 stride-1 3x3 layers (ask conv_igemm_nl_ok first)");
     }
-    if (direct_ok(CT<T>::CK == 32 ? VS_BF16 : VS_F32, pd))      // (a 32-cout form was measured in round 4: 636 vs 426 us for the tile kernel on the 32 -> 32 layer of a 128 x 512^2 batch - not kept)
-        return launch_direct<T, 16>(p, out_nchw, s);
+    ConvParams k = p;      // the point of launch: the kernels receive the fp32 bit alone, the layout bit travels in their geometry
+    k.out_f32 = p.out_f32 & 1;
+    if (plan.family == CONV_DIRECT) return launch_direct<T, 16>(k, out_nchw, s);
     if constexpr (sizeof(T) == 2) {
-        if (const int sm = stream_mode(Elem<T>::kDtype, p, out_nchw)) {
+        if (plan.family == CONV_STREAM) {
             unsigned long long* probe = vs_probe_buffer(256);
             const int stg = 0;      // (a start delay staggered by workgroup was measured neutral)
-            return sm == 64 ? ring::launch_stream<T, 64, 2, 8, 4, 2, 2>(p, probe, s, 256, stg) : ring::launch_stream<T, 32, 2, 8, 4, 2, 2>(p, probe, s, 256, stg);
+            return BN == 64 ? ring::launch_stream<T, 64, 2, 8, 4, 2, 2>(k, probe, s, 256, stg) : ring::launch_stream<T, 32, 2, 8, 4, 2, 2>(k, probe, s, 256, stg);
         }
     }
     if constexpr (std::is_same<T, bf16_t>::value) {
-        const int rm = ring_mode(VS_BF16, p, out_nchw);
-        if (rm) {
+        if (plan.family == CONV_RING) {
+            const int rm = plan.ring;
             const long groups = rm == 3 ? p.N / 2 : (long)p.N * cdiv(p.Hout, 16) * cdiv(p.Wout, 16);
-            unsigned long long* probe = vs_probe_buffer((size_t)(cdiv((int)groups, 8) * 8) * cdiv(p.Cout, rm == 1 ? 64 : 32));
+            unsigned long long* probe = vs_probe_buffer((size_t)(cdiv((int)groups, 8) * 8) * cdiv(p.Cout, BN));
             if (p.nl_bins) {
-                if (rm == 1) return ring::launch_ring<64, 2, 8, 4, 1, 2, 2, true>(p, out_nchw, probe, s);
-                if (rm == 2) return ring::launch_ring<32, 2, 8, 4, 1, 4, 2, true>(p, out_nchw, probe, s);
-                return ring::launch_ring<32, 2, 4, 3, 2, 1, 2, true>(p, out_nchw, probe, s);
+                if (rm == 1) return ring::launch_ring<64, 2, 8, 4, 1, 2, 2, true>(k, out_nchw, probe, s);
+                if (rm == 2) return ring::launch_ring<32, 2, 8, 4, 1, 4, 2, true>(k, out_nchw, probe, s);
+                return ring::launch_ring<32, 2, 4, 3, 2, 1, 2, true>(k, out_nchw, probe, s);
             }
-            if (rm == 1) return ring::launch_ring<64, 2, 8, 4, 1, 2, 2>(p, out_nchw, probe, s);
-            if (rm == 2) return ring::launch_ring<32, 2, 8, 4, 1, 4, 2>(p, out_nchw, probe, s);
-            return ring::launch_ring<32, 2, 4, 3, 2, 1, 2>(p, out_nchw, probe, s);
+            if (rm == 1) return ring::launch_ring<64, 2, 8, 4, 1, 2, 2>(k, out_nchw, probe, s);
+            if (rm == 2) return ring::launch_ring<32, 2, 8, 4, 1, 4, 2>(k, out_nchw, probe, s);
+            return ring::launch_ring<32, 2, 4, 3, 2, 1, 2>(k, out_nchw, probe, s);
         }
     }
+    VS_REQUIRE(plan.family == CONV_TILE, "conv_igemm: the plan's kernel family %d is not built for this dtype", (int)plan.family);
     VS_REQUIRE(!p.scatter, "conv_igemm: the volume-scatter epilogue needs the direct kernel (check conv_head_scatter_ok first)");
     TileGeom g;
     g.tw_shift = tile_tw(p, PT) == 16 ? 4 : 3;
@@ -1180,29 +1191,39 @@ int dispatch(const ConvParams& p, int out_nchw, hipStream_t s) {
     g.pw_magic = 0xffffffffu / (unsigned)g.PW + 1u;       // exact for x * PW < 2^32
     g.tw_magic = 0xffffffffu / (unsigned)g.tiles_w + 1u;
     g.probe = vs_probe_buffer((size_t)p.N * g.tiles_h * g.tiles_w * cdiv(p.Cout, BN));
-    if constexpr (std::is_same<T, bf16_t>::value) {
-        if (NW == 8 && p.nl_bins) {
-#define VS_CONV8N(bn) if (BN == bn) return launch_one<T, bn, 2, 9, 1, 8, 1, true>(p, g, s)
-            VS_CONV8N(64); VS_CONV8N(32); VS_CONV8N(16);
-#undef VS_CONV8N
-        }
-    }
-    if (NW == 8) {
-        const bool t9 = p.KH * p.KW == 9;
-#define VS_CONV8(bn) if (BN == bn) return t9 ? launch_one<T, bn, 2, 9, 1, 8>(p, g, s) : launch_one<T, bn, 2, 1, 1, 8>(p, g, s)
-        VS_CONV8(64); VS_CONV8(32); VS_CONV8(16);
-#undef VS_CONV8
-    }
-#define VS_CONV_CASE(bn, pt) if (BN == bn && PT == pt) return launch_tk<T, bn, pt>(p, g, s)
-    VS_CONV_CASE(64, 2); VS_CONV_CASE(64, 1);
-    VS_CONV_CASE(32, 2); VS_CONV_CASE(32, 1);
-    VS_CONV_CASE(16, 2); VS_CONV_CASE(16, 1);
-#undef VS_CONV_CASE
-    vs_set_error("conv_igemm: no kernel for BN=%d PT=%d NW=%d", BN, PT, NW);
-    return VS_ERR_UNSUPPORTED;
+    return launch_tile<T>(k, plan, g, s);
 }
 
 }  // namespace
+
+// The one place that decides which kernel a launch gets: the families in their order of priority.  p as callers hold it
+// (out_f32 packed); launch_conv_igemm and every query read what this returns.
+ConvPlan conv_plan(int dtype, const ConvParams& p) {
+    const int out_nchw = p.out_f32 >> 1, taps = p.KH * p.KW;
+    const Pick c = pick_cfg(p);
+    ConvPlan pl{};
+    pl.can_pool = c.PT >= 2 && p.Wout >= 16 && !(p.Hout & 1) && !(p.Wout & 1);   // (the ring kernel's 16 x 16 tiles: the same condition)
+    if (direct_ok(dtype, p)) {   // (a 32-cout form was measured in round 4: 636 vs 426 us for the tile kernel on the 32 -> 32 layer of a 128 x 512^2 batch - not kept)
+        pl.family = CONV_DIRECT; pl.BN = 16; pl.PT = 2; pl.NW = 4;
+        pl.stat_rows = direct_geom(p).nwaves;   // one partial row per wave
+        pl.code = 16 * 1000 + 2 * 100 + 9 * 10 + 4;
+        return pl;
+    }
+    const int sm = stream_mode(dtype, p, out_nchw), rm = ring_mode(dtype, p, out_nchw);
+    const int TW = tile_tw(p, c.PT), TH = c.NW * 16 * c.PT / TW;
+    pl.stat_rows = rm ? (rm == 3 ? p.N / 2 : p.N * cdiv(p.Hout, 16) * cdiv(p.Wout, 16)) : p.N * cdiv(p.Hout, TH) * cdiv(p.Wout, TW);
+    if (sm) {
+        pl.family = CONV_STREAM; pl.BN = sm; pl.PT = 2; pl.NW = 8;
+        pl.code = sm * 1000 + 2 * 100 + 9 * 10 + 7;
+    } else if (rm) {
+        pl.family = CONV_RING; pl.ring = rm; pl.BN = rm == 1 ? 64 : 32; pl.PT = 2; pl.NW = rm == 3 ? 4 : 8;
+        pl.code = pl.BN * 1000 + 2 * 100 + 9 * 10 + 6;
+    } else {
+        pl.family = CONV_TILE; pl.BN = c.BN; pl.PT = c.PT; pl.NW = c.NW;
+        pl.code = c.BN * 1000 + c.PT * 100 + taps * 10 + (c.NW == 8 ? 8 : (p.stride == 2 ? 2 : 1));
+    }
+    return pl;
+}
 
 bool head_dgrad_planes_ok(int dtype, int classes, int H, int W, int C) {
     return (dtype == VS_BF16 || dtype == VS_F16) && classes >= 1 && 9 * classes <= 64 && C >= 4 && C <= 16 && !(C & 3) &&
@@ -1231,26 +1252,6 @@ int launch_head_dgrad_planes(int dtype, const float* dl, const void* w, void* ou
 }
 
 
-bool conv_igemm_can_pool(const ConvParams& p) {
-    return pick_cfg(p).PT >= 2 && p.Wout >= 16 && !(p.Hout & 1) && !(p.Wout & 1);   // (the ring kernel's 16 x 16 tiles: the same condition)
-}
-
-// instantiation code of the kernel launch_conv_igemm picks: BN*1000 + PT*100 + NTAPS*10 + code
-// (code 1 = stride 1, 2 = stride 2, 4 = direct (LDS-free) shallow-layer kernel, 8 = 8-wave 256-pixel tiles)
-int conv_igemm_variant(int dtype, const ConvParams& p) {
-    if (direct_ok(dtype, p)) return 16 * 1000 + 2 * 100 + 9 * 10 + 4;
-    if (const int sm = stream_mode(dtype, p, p.out_f32 >> 1)) return sm * 1000 + 2 * 100 + 9 * 10 + 7;                    // 7 = persistent LDS-DMA ring
-    if (const int rm = ring_mode(dtype, p, p.out_f32 >> 1)) return (rm == 1 ? 64 : 32) * 1000 + 2 * 100 + 9 * 10 + 6;   // 6 = LDS-DMA ring
-    const Pick c = pick_cfg(p);
-    return c.BN * 1000 + c.PT * 100 + (p.KH * p.KW) * 10 + (c.NW == 8 ? 8 : (p.stride == 2 ? 2 : 1));
-}
-
-bool conv_head_scatter_ok(int dtype, const ConvParams& p) { return p.scatter && direct_ok(dtype, p); }
-
-// whether the kernel launch_conv_igemm picks for p can put its statistics into fixed-point bins (ConvParams::stats_bins): the
-// kernels that end in conv_epilogue (tile and ring kernels) and the direct shallow-layer kernel (one atomic pair per wave and cout)
-bool conv_igemm_bins_ok(int dtype, const ConvParams& p) { return dtype == VS_BF16; }
-
 // whether launch_conv_igemm can normalise p.src0 while loading it (ConvParams::nl_*): the register-staged tile kernel's bf16
 // stride-1 3x3 instantiations (p as the layer will be launched, nl_* set or not)
 bool conv_igemm_nl_ok(int dtype, const ConvParams& p) {
@@ -1258,37 +1259,26 @@ bool conv_igemm_nl_ok(int dtype, const ConvParams& p) {
     q.nl_bins = nullptr;
     if (dtype != VS_BF16 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.dil > 1 || p.gc || p.scatter || p.up0 == 2 || p.bz ||
         (p.C0 & 7) || p.C0 > 2048) return false;
-    if (direct_ok(dtype, q)) return false;    // the strip kernels have no such loader (yet)
-    return true;
+    return conv_plan(dtype, q).family != CONV_DIRECT;    // the strip kernels have no such loader (yet)
 }
 
-int conv_igemm_stat_rows(int dtype, const ConvParams& p) {
-    if (direct_ok(dtype, p)) return direct_geom(p).nwaves;   // one partial row per wave
-    if (const int rm = ring_mode(dtype, p, p.out_f32 >> 1)) return rm == 3 ? p.N / 2 : p.N * cdiv(p.Hout, 16) * cdiv(p.Wout, 16);
-    const Pick c = pick_cfg(p);
-    const int TW = tile_tw(p, c.PT), TH = c.NW * 16 * c.PT / TW;
-    return p.N * cdiv(p.Hout, TH) * cdiv(p.Wout, TW);
-}
-
-int launch_conv_igemm(int dtype, const ConvParams& p, hipStream_t s) {
-    const int nchw = p.out_f32 >> 1;  // out_f32: bit0 = fp32 store, bit1 = NCHW layout
-    ConvParams q = p;
-    q.out_f32 = p.out_f32 & 1;
-    if (dtype == VS_BF16) return dispatch<bf16_t>(q, nchw, s);
-    if (dtype == VS_F32) return dispatch<float>(q, nchw, s);
+int launch_conv_igemm(int dtype, const ConvParams& p, hipStream_t s, const ConvPlan* plan) {
+    const ConvPlan pl = plan ? *plan : conv_plan(dtype, p);
+    if (dtype == VS_BF16) return dispatch<bf16_t>(p, pl, s);
+    if (dtype == VS_F32) return dispatch<float>(p, pl, s);
     if (dtype == VS_F16) {
-        VS_REQUIRE(!q.bz && !q.stats_partial && !q.pool0, "conv_igemm: fp16 is the inference precision (no training epilogues)");
-        return dispatch<f16_t>(q, nchw, s);
+        VS_REQUIRE(!p.bz && !p.stats_partial && !p.pool0, "conv_igemm: fp16 is the inference precision (no training epilogues)");
+        return dispatch<f16_t>(p, pl, s);
     }
     vs_set_error("conv_igemm: bad dtype %d", dtype);
     return VS_ERR_INVALID;
 }
 
 // Whether two chained evaluation-mode layers - p's output (NHWC, storage type) read by q and by nothing else - can run as ONE launch of
-// conv_direct_pair_kernel: both are strip-kernel layers on their own (direct_ok), 16-bit storage, at most 16 channels between them.
+// conv_direct_pair_kernel: both are strip-kernel layers on their own (CONV_DIRECT), 16-bit storage, at most 16 channels between them.
 bool conv_pair_ok(int dtype, const ConvParams& p, const ConvParams& q) {
     if ((dtype != VS_BF16 && dtype != VS_F16) || !vs_option("conv_pair")) return false;
-    if (!direct_ok(dtype, p) || !direct_ok(dtype, q)) return false;
+    if (conv_plan(dtype, p).family != CONV_DIRECT || conv_plan(dtype, q).family != CONV_DIRECT) return false;
     if (p.pool0 || q.pool0 || p.scatter || q.scatter || p.out_f32 || q.out_f32 || p.stats_partial || p.stats_bins || q.stats_partial || q.stats_bins ||
         q.up0 || q.C1 || p.Cout > 16 || q.Cout > 16 || (p.Cout & 7) || (q.Cout & 3)) return false;
     return q.C0 == p.Cout && q.N == p.N && q.Hin == p.Hout && q.Win == p.Wout && q.Hout == p.Hout && q.Wout == p.Wout;

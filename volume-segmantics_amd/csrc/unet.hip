@@ -15,67 +15,6 @@
 #include "common.h"
 #include "prof.h"
 
-int launch_weight_prepare(int dtype, const float* w, void* wc, void* wt, int cout, int taps, int cin, int cout_pad, hipStream_t s);
-int launch_dlogits_to_nhwc16(int dtype, const float* d, void* o, int n, int k, int64_t hw, float* db, float* partial, hipStream_t s);
-extern "C" int vs_depth_to_space2(int dtype, const void* x, void* y, int n, int h, int w, int c, const float* bias, const float* scale,
-                                  const float* shift, int relu, void* stream);
-extern "C" int vs_space_to_depth2(int dtype, const void* x, void* y, int n, int h, int w, int c, void* stream);
-extern "C" int vs_colsum(int dtype, const void* x, int64_t rows, int c, float* out, float* workspace, size_t workspace_bytes, void* stream);
-extern "C" int vs_upsample2x_add(int dtype, const void* x, const void* skip, void* y, int n, int h, int w, int c, void* stream);
-extern "C" size_t vs_gn_bwd_workspace(int n, int c, int groups);
-extern "C" int vs_gn_fwd(int dtype, const void* x, const float* gamma, const float* beta, int relu, void* y, float* stats, int n, int64_t hw,
-                         int c, int groups, float eps, float* workspace, size_t workspace_bytes, void* stream);
-extern "C" int vs_gn_bwd(int dtype, const void* dy, const void* x, const float* stats, const float* gamma, const float* beta, int relu,
-                         void* dx, float* dgamma, float* dbeta, int n, int64_t hw, int c, int groups, float* workspace,
-                         size_t workspace_bytes, void* stream);
-extern "C" int vs_bilinear_up(int dtype, const void* x, void* y, int n, int h, int w, int c, int factor, void* stream);
-extern "C" int vs_bilinear_up_bwd(int dtype, const void* dy, void* dx, int n, int h, int w, int c, int factor, int accumulate, void* stream);
-extern "C" int vs_bilinear_up_planes(const float* x, float* y, int planes, int h, int w, int factor, void* stream);
-extern "C" int vs_bilinear_up_planes_bwd(const float* dy, float* dx, int planes, int h, int w, int factor, void* stream);
-extern "C" int vs_dropout2d_mask(float* mask, int n, int c, float p, uint32_t seed, const int64_t* counter, int64_t bias, void* stream);
-extern "C" int vs_channel_scale(int dtype, const void* x, const float* mask, void* y, int n, int64_t hw, int c, void* stream);
-extern "C" int vs_dwconv3x3(int dtype, const void* x, const float* w, void* y, int n, int h, int wd, int c, int dilation, int flip, void* stream);
-extern "C" size_t vs_dwconv3x3_wgrad_workspace(int c);
-extern "C" int vs_dwconv3x3_wgrad(int dtype, const void* x, const void* dy, float* dw, int n, int h, int wd, int c, int dilation, float* workspace,
-                                  size_t workspace_bytes, void* stream);
-extern "C" int vs_spatial_sum(int dtype, const void* x, void* y, int n, int64_t hw, int c, float scale, void* stream);
-extern "C" int vs_broadcast_rows(int dtype, const void* v, void* y, int n, int64_t hw, int c, float scale, int accumulate, void* stream);
-extern "C" int vs_dropout(int dtype, const void* x, void* y, int64_t elems, float p, uint32_t seed, const int64_t* counter, int64_t bias, void* stream);
-extern "C" int vs_dilated_im2col(int dtype, const void* src, void* dst, int n, int h, int w, int c, int r, int inverse, int accumulate, void* stream);
-extern "C" int vs_pab_attention_fwd(int dtype, const void* top, const void* center, const void* bottom, const void* x, void* y, float* sp,
-                                    float* scratch, int n, int hw, int K, int C, void* stream);
-extern "C" int vs_pab_attention_bwd(int dtype, const void* dy, const void* top, const void* center, const void* bottom, const float* sp, void* dtop,
-                                    void* dcenter, void* dbottom, float* scratch, int n, int hw, int K, int C, void* stream);
-extern "C" size_t vs_pab_scratch_bytes(int n, int hw, int C);
-extern "C" int vs_se_gate_fwd(int dtype, const void* p, const float* w1, const float* b1, const float* w2, const float* b2, void* a, float* hid,
-                              int n, int C, int R, int swish, void* stream);
-extern "C" int vs_se_gate_bwd(int dtype, const void* da, const void* a, const void* p, const float* hid, const float* w1, const float* w2, void* dp,
-                              float* dw1, float* db1, float* dw2, float* db2, float* scratch, int n, int C, int R, int swish, void* stream);
-extern "C" size_t vs_se_gate_scratch_floats(int n, int C, int R);
-extern "C" int vs_channel_gate(int dtype, const void* x, const void* g, void* y, int n, int64_t hw, int c, void* stream);
-extern "C" int vs_channel_dot(int dtype, const void* x, const void* dy, void* dg, int n, int64_t hw, int c, void* stream);
-extern "C" int vs_maxpool2x2(int dtype, const void* x, void* y, int n, int h, int w, int c, void* stream);
-extern "C" int vs_maxpool2x2_bwd(int dtype, const void* x, const void* dy, void* dx, int n, int h, int w, int c, int accumulate, void* stream);
-extern "C" int vs_conv_to_plane(int dtype, const void* x, const float* w, const float* bias, float* z, int n, int h, int wd, int c, int k, void* stream);
-extern "C" int vs_conv_to_plane_bwd(int dtype, const void* x, const float* w, const float* dz, void* dx, float* dw, float* db, int n, int h, int wd,
-                                    int c, int k, void* stream);
-extern "C" size_t vs_fpa_arena_floats(int n, int h, int w);
-extern "C" size_t vs_fpa_dz1_offset(int n, int h, int w);
-extern "C" int vs_fpa_pyramid_fwd(float* arena, float* plane, float* const* params, int n, int h, int w, int training, void* stream);
-extern "C" int vs_fpa_pyramid_bwd(float* arena, const float* dplane, float* const* params, float* const* grads, int n, int h, int w, void* stream);
-extern "C" int vs_fpa_combine(int dtype, const float* plane, const void* mid, const void* b1, void* out, int n, int64_t hw, int c, void* stream);
-extern "C" int vs_fpa_combine_bwd(int dtype, const void* dy, const float* plane, const void* mid, void* dmid, float* dplane, int n, int64_t hw, int c,
-                                  void* stream);
-extern "C" int vs_sigmoid(int dtype, const void* x, void* y, int64_t elems, void* stream);
-extern "C" int vs_sigmoid_bwd(int dtype, const void* dy, const void* y, void* dx, int64_t elems, void* stream);
-extern "C" int vs_bn_fold_bias(const float* scale, const float* bias, float* shift, int c, void* stream);
-int launch_adamw_prepare_all(int dtype, const vs_adamw_args& a, const float* grads, void* ws, int n, const long* w_off, const long* wc_off,
-                             const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad, const int* cg,
-                             const int* update, hipStream_t s);
-int launch_weight_prepare_all(int dtype, const float* params, void* ws, int n, const long* w_off, const long* wc_off,
-                              const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad,
-                              const int* cg, hipStream_t s);
-
 namespace {
 
 struct TensorInfo {
@@ -1860,7 +1799,8 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
                 p.nl_gamma = c.P(q.bn_idx); p.nl_beta = c.P(q.bn_idx + 1);
                 p.nl_y = c.a(u.src0);      // the activation the weight gradient reads: this launch's by-product
             }
-            prof_set_variant(conv_igemm_variant(dt, p));
+            const ConvPlan plan = conv_plan(dt, p);     // (before the epilogue fields are set: a launch behind one of those decides again)
+            prof_set_variant(plan.code);
             ProfScope prof(PK_CONV_FWD, conv_flops(c, u), 0, c.s);
             prof_set_variant(0);
             if (u.bn_idx < 0 && u.gn_idx < 0) {   // plain biased convolution (FPN's lateral 1x1s): no norm, no activation
@@ -1868,7 +1808,7 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
                 // its BatchNorm is the next unit (U_BN): the batch statistics come straight from the fp32 accumulators, as for the fused units
                 if (training && dt == VS_BF16 && u.bias_idx < 0 && unit_index + 1 < (int)net->units.size() &&
                     net->units[unit_index + 1].kind == U_BN && net->units[unit_index + 1].src0 == u.out) {
-                    const int rows_needed = conv_igemm_stat_rows(dt, p);
+                    const int rows_needed = plan.stat_rows;
                     if (rows_needed > 0 && (size_t)rows_needed * 2 * u.cout * sizeof(float) <= net->bnws_bytes) {
                         p.stats_partial = (float*)(c.ws + net->off_bnws);
                         carried_stat_rows = rows_needed;
@@ -1887,7 +1827,7 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
             if (u.colr && (rc = vs_dilated_im2col(dt, c.a(u.src0), c.ws + u.off_xs, n, u.hin, u.win, u.cin0, u.colr, 0, 0, stream))) return rc;
             if (u.gn_idx >= 0) {                  // convolution + GroupNorm + ReLU (per-sample statistics: nothing folds in evaluation)
                 p.out = training ? c.z(u.out) : (void*)(c.ws + net->off_gnz);
-                if ((rc = launch_conv_igemm(dt, p, c.s))) return rc;
+                if ((rc = launch_conv_igemm(dt, p, c.s, &plan))) return rc;
                 if ((rc = vs_gn_fwd(dt, p.out, c.P(u.gn_idx), c.P(u.gn_idx + 1), u.relu, c.a(u.out), (float*)(c.ws + u.off_gn), n,
                                     (int64_t)u.hout * u.wout, u.cout, u.gn_groups, 1e-5f, (float*)(c.ws + net->off_gnws), net->gnws_bytes, stream))) return rc;
                 continue;
@@ -1896,8 +1836,8 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
                 p.out = c.z(u.out);
                 if (u.bias_idx >= 0) p.shift = c.P(u.bias_idx);   // smp's ConvBnRelu keeps the convolution's bias: z includes it
                 if (dt == VS_BF16 && u.bias_idx < 0) {  // batch statistics straight from the fp32 accumulators
-                    const int rows_needed = conv_igemm_stat_rows(dt, p);
-                    const bool bins_ok = u.bn_idx >= 0 && vs_option("stats_bins") && net->bins_bytes && conv_igemm_bins_ok(dt, p);
+                    const int rows_needed = plan.stat_rows;
+                    const bool bins_ok = u.bn_idx >= 0 && vs_option("stats_bins") && net->bins_bytes;   // (every bf16 kernel has them)
                     const bool nl = bins_ok && nl_consumer(c, unit_index) >= 0;
                     if (bins_ok && (nl || net->stats_hook || rows_needed > vs_option("bn_inline_rows"))) {
                         // many tiles: their sums go into a few rows of fixed-point bins, finalised inside the apply sweep -
@@ -1975,9 +1915,10 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
             }
             if (scatter) {
                 p.scatter = scatter;
-                if (conv_head_scatter_ok(dt, p)) {
+                const ConvPlan plan = conv_plan(dt, p);
+                if (conv_head_scatter_ok(p, plan)) {
                     p.out = nullptr;
-                    if ((rc = launch_conv_igemm(dt, p, c.s))) return rc;
+                    if ((rc = launch_conv_igemm(dt, p, c.s, &plan))) return rc;
                     head_scattered = true;
                     continue;
                 }
@@ -2641,13 +2582,14 @@ static int unet_backward_range(vs_unet_t* net, const float* params, const float*
             const bool acc0 = written[u.src0] != 0;
             VS_REQUIRE(u.src1 < 0 || !written[u.src1], "backward: decoder skip gradient written twice");
             if (u.src1 >= 0) { p.out1 = c.da(u.src1); p.split_c = u.cin0; written[u.src1] = 1; }
-            if (!acc0 && conv_igemm_can_pool(p)) {  // 2x2 sum of the upsampled part inside the dgrad epilogue
+            if (!acc0 && conv_plan(dt, p).can_pool) {  // 2x2 sum of the upsampled part inside the dgrad epilogue
                 p.pool0 = 1;
                 p.out = c.da(u.src0);
-                prof_set_variant(conv_igemm_variant(dt, p));
+                const ConvPlan plan = conv_plan(dt, p);
+                prof_set_variant(plan.code);
                 ProfScope prof(PK_CONV_DGRAD, conv_flops(c, u), 0, c.s);
                 prof_set_variant(0);
-                if ((rc = launch_conv_igemm(dt, p, c.s))) return rc;
+                if ((rc = launch_conv_igemm(dt, p, c.s, &plan))) return rc;
             } else {
                 p.out = c.ws + net->off_dup;
                 {
@@ -2669,10 +2611,11 @@ static int unet_backward_range(vs_unet_t* net, const float* params, const float*
             // the tail of every workgroup, which costs about what the separate, fully coalesced sweep cost.  Layers the direct kernel takes
             // are left alone (it has no such epilogue; falling back to the tile kernel cost 55 us each).
             const int pa = u.src0, pu = net->producer[pa];
+            ConvPlan plan = conv_plan(dt, p);
             if (vs_option("fuse_bn_bwd") && pu >= 0 && pu == ui - 1 && net->first_consumer[pa] == ui && net->units[pu].kind == U_CONV &&
-                net->units[pu].bn_idx >= 0 && !(p.Cout & 3) && conv_igemm_variant(dt, p) % 10 != 4) {
+                net->units[pu].bn_idx >= 0 && !(p.Cout & 3) && plan.family != CONV_DIRECT) {
                 const Unit& q = net->units[pu];
-                const int rows_needed = conv_igemm_stat_rows(dt, p);
+                const int rows_needed = plan.stat_rows;
                 // (fixed-point bins for these sums - no finalize launch - were measured in round 3: -0.013 ms per step, and they are not
                 // scale-equivariant (gradients of 2 g != 2 x gradients of g bit for bit): not kept)
                 if ((size_t)rows_needed * 2 * q.cout * sizeof(float) <= net->bnws_bytes) {
@@ -2684,12 +2627,13 @@ static int unet_backward_range(vs_unet_t* net, const float* params, const float*
                     p.bstats_partial = (float*)(c.ws + net->off_bnws);
                     p.brelu = q.relu;
                     net->bwd_stat_rows[pa] = rows_needed;
+                    plan = conv_plan(dt, p);      // bz is set: the BN-backward epilogue narrows the choice
                 }
             }
-            prof_set_variant(conv_igemm_variant(dt, p));
+            prof_set_variant(plan.code);
             ProfScope prof(PK_CONV_DGRAD, u.kind == U_HEAD ? 2.0 * n * u.hout * u.wout * net->classes * u.k * u.k * u.cin0 : conv_flops(c, u), 0, c.s);
             prof_set_variant(0);
-            if ((rc = launch_conv_igemm(dt, p, c.s))) return rc;
+            if ((rc = launch_conv_igemm(dt, p, c.s, &plan))) return rc;
             written[u.src0] = 1;
         }
         }
@@ -2815,8 +2759,7 @@ extern "C" int vs_unet_nl_plan(vs_unet_t* net, int n, int* flags, int cap) {
         if (i < cap) flags[i] = 0;
         if (u.kind != U_CONV || net->dtype != VS_BF16 || u.bn_idx < 0 || u.gn_idx >= 0 || u.bias_idx >= 0) continue;
         if (!vs_option("stats_bins") || !net->bins_bytes) continue;
-        ConvParams p = conv_params(c, u);
-        if (!conv_igemm_bins_ok(net->dtype, p) || nl_consumer(c, i) < 0) continue;
+        if (nl_consumer(c, i) < 0) continue;   // (the unit is bf16: its kernel, whichever it is, has statistics bins)
         act[u.out] = 1;
         if (i < cap) flags[i] = 1;
     }
