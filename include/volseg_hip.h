@@ -265,6 +265,10 @@ typedef int (*vs_stats_hook_t)(void* user, void* values, int64_t count, int kind
 int vs_unet_set_stats_hook(vs_unet_t* net, vs_stats_hook_t hook, void* user, int world);
 int vs_unet_debug_unit(const vs_unet_t* net, int unit, char* weight_name, int name_len, int* c, int* h, int* w,
                        size_t* off_a, size_t* off_z, size_t* off_da, size_t* off_dz);
+/* The whole plan as line-oriented text (name=value): one header line, then one line per tensor, activation and unit with every field
+ * of each - two builds construct the same plan exactly when the texts are equal (tools/unet_plan_sweep.py).  Writes at most `cap`
+ * bytes (no terminator) and returns the bytes needed.  Host logic only. */
+size_t vs_unet_plan_dump(const vs_unet_t* net, char* buf, size_t cap);
 
 /* Per-kernel-class timing with HIP events recorded on the launch stream (bench.py's roofline block).
  * vs_profile_enable(1) clears and starts collecting; vs_profile_read sums, per kind, the elapsed ms, the

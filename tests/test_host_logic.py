@@ -513,6 +513,39 @@ def test_conv_plan_codes_and_stat_rows_of_the_headline_launches():
         assert got == (code, stat_rows), (n, hw, c0, c1, up0, cout, k, stride, out_f32, split_c, block, got)
 
 
+def test_every_network_plan_is_the_recorded_one():
+    """vs_unet_plan_dump (host logic, nothing is launched) through tools/unet_plan_sweep.py: for each of the 56 supported (topology, encoder)
+    pairs one SHA-256 over the dumps of its 27 plans (fp32 / bf16 / fp16 x classes 1 / 3 / 16 x (1, 32, 32) / (2, 64, 96) / (32, 256, 256)) -
+    every field of every unit, every activation id, every tensor of the state-dict layout and every workspace offset.  The rows (code, first
+    16 hex digits) were recorded from the build BEFORE plan construction moved to shared unit constructors, with the same dump function
+    compiled into it.  A pull request that means to change a plan re-records that pair's row in the same commit; any other mismatch is a
+    plan that moved by accident: `tools/unet_plan_sweep.py LIB --dump DIR` on both builds and `diff -r` name the field."""
+    import importlib.util
+    from pathlib import Path
+
+    from volume_segmantics_amd import _lib as L
+
+    recorded = (
+    (18, "c55bec059ffd6d4e"), (34, "c409754c7d964c77"), (50, "92575106b3d24403"), (51, "f540448efc3691cd"), (103, "cc50e1cc04fe9949"), (104, "c44fbae9f5680be7"), (150, "5d7d84d30d536f72"), (201, "cfddacb31d743c52"),
+    (1018, "fcfde8876c45ba8a"), (1034, "b4fa8661e9007740"), (1050, "eef7a8cd101dd6fb"), (1051, "d3dfd9454d129f7f"), (1103, "20338903ca41715f"), (1104, "c8d1aa0f00257e59"), (1150, "8a2192f341a330ff"), (1201, "e7164fba97bb9537"),
+    (2018, "18febe50405d2388"), (2034, "6a1f9fdf34c2404a"), (2050, "1441c11014757fab"), (2051, "09d5063da26392c9"), (2150, "4e9aa29a22de05e8"), (2201, "0cd031d3919a22a4"), (3018, "a4bddbb0b0dc112c"), (3034, "1f8cb2f6e1b2db67"),
+    (3050, "731f4e291a77bda3"), (3051, "83281e3014fe55b7"), (3103, "9e94ddb533ee08e9"), (3104, "6178f8e9feb5966b"), (3150, "b6e17e7d1e45b8df"), (3201, "bfd08dd31d410aac"), (4018, "b8f1c528a4aa3145"), (4034, "61fb2091d5de2484"),
+    (4050, "7f304b5b56bb6d42"), (4051, "5cd27590b591407d"), (4103, "a10b8e6462e0b7ab"), (4104, "95853af3b6eb5327"), (5018, "ad9a60ae88a746f5"), (5034, "06b697da6b44cb1d"), (5050, "f87b50955e6f6aef"), (5051, "1e563f3f8a023525"),
+    (5103, "3623c114168684ab"), (5104, "dc6ca84a47b2d77d"), (6018, "abca7a476c094def"), (6034, "4a91124f64005460"), (6050, "be213d608ce11d8e"), (6051, "769efd04314d467d"), (6103, "0779c30dd04039e5"), (6104, "7de365c2e3e151d5"),
+    (6150, "6003c5a491d5984c"), (6201, "d2f7252eac8589d1"), (7018, "b44cfc44726fb3b0"), (7034, "eb262373dafb61b1"), (7050, "fce436bbbc1108df"), (7051, "e07a4c98a2050149"), (7103, "6b2858f2d3809ba6"), (7104, "38fae1249c2219f3"),
+    )
+    assert len(recorded) == 56
+    tool = Path(__file__).resolve().parent.parent / "tools" / "unet_plan_sweep.py"
+    spec = importlib.util.spec_from_file_location("unet_plan_sweep", tool)
+    sweep = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(sweep)
+    got = sweep.sweep(sweep.load(L.LIB_PATH))
+    assert sorted(got) == [code for code, _ in recorded], sorted(got)
+    for code, digest in recorded:
+        assert got[code][:16] == digest, (f"the plans of topology {code // 1000} / encoder {code % 1000} (code {code}) are not the recorded ones: "
+                                          f"{got[code][:16]} != {digest} - compare `python tools/unet_plan_sweep.py LIB --dump DIR` of both builds")
+
+
 def test_sync_batchnorm_hook_is_accepted_only_where_it_is_built():
     """vs_unet_set_stats_hook (host logic): bf16 plans whose BatchNorms all sit behind bias-free convolutions / the ResNet stem take
     the cross-rank statistics hook (U-Net, U-Net++ / ResNet-50 = BASELINE configs[3], FPN); fp32 plans and networks with BatchNorm

@@ -213,6 +213,7 @@ _SIGS = {
     "vs_unet_set_stats_hook": (I, [P, P, P, I]),
     "vs_unet_debug_unit": (I, [P, I, C.c_char_p, I, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(SZ), C.POINTER(SZ),
                                C.POINTER(SZ), C.POINTER(SZ)]),
+    "vs_unet_plan_dump": (SZ, [P, C.c_char_p, SZ]),
     "vs_profile_enable": (I, [I]),
     "vs_profile_enabled": (I, []),
     "vs_profile_num_kinds": (I, []),

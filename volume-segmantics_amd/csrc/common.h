@@ -339,12 +339,12 @@ int launch_conv_wgrad(int dtype, const WgradParams& p, hipStream_t s);
 // dw[i] = sum_k partials[k*n + i], fixed summation order
 int launch_slab_reduce(const float* partials, float* dw, size_t n, int nparts, hipStream_t s);
 // the lane-group count G of the slab_reduce4_kernel<G> launch_slab_reduce picks for (n, nparts) - 1, 4 or 16 - or 0 when it takes the
-// scalar kernel (n not a multiple of 4, unaligned buffers): a launch that sums several layers' slabs at once uses the same body
+// scalar kernel (n not a multiple of 4, unaligned buffers)
 int slab_reduce_groups(const float* partials, const float* dw, size_t n, int nparts);
 // dw = sum over the split-K slabs, 16 bytes per lane: thread (j, g) of a block sums slabs g, g + G, g + 2 G, .. of four
 // consecutive outputs (two accumulators, four loads in flight), the G groups of an output meet in LDS in a fixed order -
 // bitwise reproducible.  G widens the grid for the small tensors (64 x 9 x 64 outputs summed over 128 slabs).  `bid` = the block's
-// index among the cdiv(n4, 256 / G) blocks of this tensor (a per-layer launch passes blockIdx.x, the per-group launch its offset).
+// index among the cdiv(n4, 256 / G) blocks of this tensor (slab_reduce4_kernel, its one user, passes blockIdx.x).
 template <int G>
 __device__ __forceinline__ void slab_reduce4_body(const float4* __restrict__ partials, float4* __restrict__ dw, size_t n4, int nparts, unsigned bid) {
     constexpr int J = 256 / G;
@@ -382,13 +382,13 @@ struct AdamwRanges { int n; long off[160]; long len[160]; };   // passed to the 
 int launch_adamw_slice(const vs_adamw_args& a, const float* grads, int64_t off, int64_t n, hipStream_t s);
 int launch_adamw_ranges(const vs_adamw_args& a, const float* grads, const AdamwRanges& r, hipStream_t s);
 int launch_weight_prepare(int dtype, const float* w, void* wc, void* wt, int cout, int taps, int cin, int cout_pad, hipStream_t s);
-// every layer's copies in one launch (per-layer HOST arrays of n entries), and the same behind the AdamW update of the weights
-int launch_weight_prepare_all(int dtype, const float* params, void* ws, int n, const long* w_off, const long* wc_off,
-                              const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad,
-                              const int* cg, hipStream_t s);
-int launch_adamw_prepare_all(int dtype, const vs_adamw_args& a, const float* grads, void* ws, int n, const long* w_off, const long* wc_off,
-                             const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad, const int* cg,
-                             const int* update, hipStream_t s);
+// one convolution's weight copies: element offset of its fp32 weight in params, BYTE offsets of the copies in the workspace (-1 = none),
+// the weight's [cout][taps][cin], cout_pad = output channels of the transposed copy, cg = channels per group (0 dense, 255 two groups),
+// update = the fused optimiser step runs AdamW on the weight (0 = frozen: copies only; the plain copy launch ignores it)
+struct WeightCopyRow { long w_off, wc_off, wt_off; int cout, taps, cin, cout_pad, cg, update; };
+// every layer's copies in one launch (n <= 64 host rows), and the same behind the AdamW update of the weights
+int launch_weight_prepare_all(int dtype, const float* params, void* ws, const WeightCopyRow* rows, int n, hipStream_t s);
+int launch_adamw_prepare_all(int dtype, const vs_adamw_args& a, const float* grads, void* ws, const WeightCopyRow* rows, int n, hipStream_t s);
 int launch_dlogits_to_nhwc16(int dtype, const float* d, void* o, int n, int k, int64_t hw, float* db, float* partial, hipStream_t s);
 // grouped convolution (cg channels per group, cin == cout): fp32 [cout][taps][cg] -> the block-expanded [cout][taps][32] copy
 // and its flipped / transposed twin [cin][taps reversed][32] (32-channel super-groups; zeros outside a group's own block)

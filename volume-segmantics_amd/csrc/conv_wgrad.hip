@@ -737,7 +737,7 @@ int dispatch(const WgradParams& p, hipStream_t s) {
 
 }  // namespace
 
-// (slab_reduce4_body<G> lives in common.h; the per-layer kernel below is its one user)
+// (slab_reduce4_body<G> lives in common.h)
 template <int G>
 __global__ __launch_bounds__(256) void slab_reduce4_kernel(const float4* __restrict__ partials, float4* __restrict__ dw, size_t n4, int nparts) {
     slab_reduce4_body<G>(partials, dw, n4, nparts, blockIdx.x);

@@ -176,8 +176,7 @@ __global__ void weight_prepare_all_kernel(float* __restrict__ params, char* __re
                                           float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq, float lr, float b1, float b2, float eps,
                                           float wd, float bc1, float bc2_sqrt, const float* __restrict__ hyper) {
     __shared__ float tile[32][33];
-    // (the grid may be capped below the tile count - launch_adamw_prepare_all: a training step's optimiser launches share the chip with
-    // the backward pass and need not finish fast - so a block walks tiles blockIdx.x, + gridDim.x, ..)
+    // (both launches bring one block per tile; a block of a smaller grid would walk tiles blockIdx.x, + gridDim.x, ..)
     int l = 0;
     for (int tb = blockIdx.x; tb < t.first_block[t.n]; tb += gridDim.x) {
         while (l + 1 < t.n && tb >= t.first_block[l + 1]) ++l;
@@ -369,27 +368,27 @@ int launch_weight_prepare_grouped(int dtype, const float* w, void* wc, void* wt,
     return VS_OK;
 }
 
-static int fill_prep_table(PrepTable& t, int n, const long* w_off, const long* wc_off, const long* wt_off, const int* cout, const int* taps,
-                           const int* cin, const int* cout_pad, const int* cg) {
+// the kernel's table of the rows; fused: with the rows' update flags (the plain copy launch leaves them 0)
+static int fill_prep_table(PrepTable& t, const WeightCopyRow* rows, int n, bool fused) {
     VS_REQUIRE(n <= 64, "weight_prepare_all: too many layers (%d)", n);
     t.n = n;
     int blocks = 0;
     for (int i = 0; i < n; ++i) {
+        const WeightCopyRow& r = rows[i];
         t.first_block[i] = blocks;
-        t.w_off[i] = w_off[i]; t.wc_off[i] = wc_off[i]; t.wt_off[i] = wt_off[i];
-        t.cout[i] = (short)cout[i]; t.cin[i] = (short)cin[i]; t.cout_pad[i] = (short)cout_pad[i]; t.taps[i] = (unsigned char)taps[i];
-        t.cg[i] = (unsigned char)(cg ? cg[i] : 0);
-        blocks += cdiv(cin[i], 32) * ((t.cg[i] && t.cg[i] != 255) ? 1 : cdiv(cout_pad[i] > cout[i] ? cout_pad[i] : cout[i], 32)) * taps[i];
+        t.w_off[i] = r.w_off; t.wc_off[i] = r.wc_off; t.wt_off[i] = r.wt_off;
+        t.cout[i] = (short)r.cout; t.cin[i] = (short)r.cin; t.cout_pad[i] = (short)r.cout_pad; t.taps[i] = (unsigned char)r.taps;
+        t.cg[i] = (unsigned char)r.cg;
+        if (fused) t.update[i] = (unsigned char)r.update;
+        blocks += cdiv(r.cin, 32) * ((t.cg[i] && t.cg[i] != 255) ? 1 : cdiv(r.cout_pad > r.cout ? r.cout_pad : r.cout, 32)) * r.taps;
     }
     t.first_block[n] = blocks;
     return VS_OK;
 }
 
-int launch_weight_prepare_all(int dtype, const float* params, void* ws, int n, const long* w_off, const long* wc_off,
-                              const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad,
-                              const int* cg, hipStream_t s) {
+int launch_weight_prepare_all(int dtype, const float* params, void* ws, const WeightCopyRow* rows, int n, hipStream_t s) {
     PrepTable t{};
-    int rc = fill_prep_table(t, n, w_off, wc_off, wt_off, cout, taps, cin, cout_pad, cg);
+    int rc = fill_prep_table(t, rows, n, false);
     if (rc) return rc;
     VS_FOR_T(dtype, hipLaunchKernelGGL((weight_prepare_all_kernel<T, false>), dim3(t.first_block[n]), dim3(256), 0, s, const_cast<float*>(params), (char*)ws, t,
                                        (float*)nullptr, (float*)nullptr, (float*)nullptr, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, (const float*)nullptr));
@@ -400,13 +399,10 @@ int launch_weight_prepare_all(int dtype, const float* params, void* ws, int n, c
 // The optimiser step of a parameter group's convolution weights and the derivation of their copies for the next forward in ONE
 // launch: per weight  AdamW element update (gradient from the flat buffer)  ->  fp32 master, low-precision copy, flipped /
 // transposed copy.  update[i] == 0 (a frozen layer): copies only.  Replaces the AdamW launch over the group's slice + the copy launch.
-int launch_adamw_prepare_all(int dtype, const vs_adamw_args& a, const float* grads, void* ws, int n, const long* w_off, const long* wc_off,
-                             const long* wt_off, const int* cout, const int* taps, const int* cin, const int* cout_pad, const int* cg,
-                             const int* update, hipStream_t s) {
+int launch_adamw_prepare_all(int dtype, const vs_adamw_args& a, const float* grads, void* ws, const WeightCopyRow* rows, int n, hipStream_t s) {
     PrepTable t{};
-    int rc = fill_prep_table(t, n, w_off, wc_off, wt_off, cout, taps, cin, cout_pad, cg);
+    int rc = fill_prep_table(t, rows, n, true);
     if (rc) return rc;
-    for (int i = 0; i < n; ++i) t.update[i] = (unsigned char)update[i];
     const float bc1 = 1.f - powf(a.beta1, (float)a.step);
     const float bc2s = sqrtf(1.f - powf(a.beta2, (float)a.step));
     const int blocks = t.first_block[n];      // (a capped grid - a slower optimiser that leaves the chip to the backward pass - was measured: 192

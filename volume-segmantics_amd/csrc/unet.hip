@@ -253,239 +253,277 @@ static int acquire_side_streams(vs_unet* net, hipStream_t caller) {
 
 namespace {
 
-int build(vs_unet* net) {
-    Layout& L = net->layout;
-    auto& A = net->acts;
-    auto& U = net->units;
-    const int H = net->h, W = net->w;
-    auto new_act = [&](int c, int h, int w, bool has_z) {
+// ---- plan construction ------------------------------------------------------------------------------------------------------------
+// A plan is three ordered lists: the tensors of the state dict (Layout), the activations and the units.  Tensor indices fix the
+// state-dict layout, activation ids fix every workspace offset, the unit order is the forward order.  The three orders are independent
+// of one another, and each is part of a construction: WHEN a constructor registers its tensors, allocates its output and emits its unit
+// is stated where it differs from "all three at once" (tests/test_host_logic.py test_every_network_plan_is_the_recorded_one pins them).
+struct Builder {
+    vs_unet* net;
+    Layout& L;
+    std::vector<Act>& A;
+    std::vector<Unit>& U;
+    explicit Builder(vs_unet* n) : net(n), L(n->layout), A(n->acts), U(n->units) {}
+
+    int act(int c, int h, int w, bool has_z) {
         Act a; a.c = c; a.h = h; a.w = w; a.has_z = has_z;
         A.push_back(a);
         return (int)A.size() - 1;
+    }
+    int tensor(const std::string& name, std::initializer_list<int64_t> shape, int kind) {
+        add_tensor(L, name, shape, kind);
+        return (int)L.tensors.size() - 1;
+    }
+    int weight(const std::string& name, std::initializer_list<int64_t> shape) { return tensor(name, shape, 0); }
+    int bias(const std::string& name, int c) { return tensor(name, {c}, 3); }
+    int bn(const std::string& prefix, int c) { return add_bn(L, prefix, c); }   // index of gamma
+
+    // a convolution described - k x k, padding k / 2, h x w -> h / stride x w / stride, ReLU - with nothing registered or allocated yet
+    static Unit conv(int src, int cin, int cout, int k, int stride, int h, int w) {
+        Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2; u.stride = stride;
+        u.hin = h; u.win = w; u.hout = h / stride; u.wout = w / stride;
+        return u;
+    }
+    // cin_w: input channels of one filter where that is not cin0 (grouped convolutions)
+    void attach_weight(Unit& u, const std::string& name, int cin_w = 0) { u.w_idx = weight(name, {u.cout, cin_w ? cin_w : u.cin0, u.k, u.k}); }
+    void attach_bias(Unit& u, const std::string& name) { u.bias_idx = bias(name, u.cout); }
+    void attach_bn(Unit& u, const std::string& prefix) { u.bn_idx = bn(prefix, u.cout); }
+    void attach_gn(Unit& u, const std::string& prefix, int groups) {
+        u.gn_groups = groups;
+        u.gn_idx = tensor(prefix + ".weight", {u.cout}, 1);
+        tensor(prefix + ".bias", {u.cout}, 2);
+    }
+    int emit(const Unit& u) { U.push_back(u); return u.out; }
+
+    // THE convolution constructor: described as conv(), its tensors registered in state-dict order - weight, bias (name not empty),
+    // BatchNorm (prefix not empty) - and its output ALLOCATED, with a pre-norm tensor z where a norm follows.  The caller sets what
+    // differs (relu, freeze flags, dilation ..) and emits it - at once, or after other units whose activations then get higher ids.
+    Unit conv_unit(const std::string& wname, const std::string& bias_name, const std::string& bn_prefix, int src, int cin, int cout, int k,
+                   int stride, int h, int w, int cin_w = 0) {
+        Unit u = conv(src, cin, cout, k, stride, h, w);
+        attach_weight(u, wname, cin_w);
+        if (!bias_name.empty()) attach_bias(u, bias_name);
+        if (!bn_prefix.empty()) attach_bn(u, bn_prefix);
+        u.out = act(cout, u.hout, u.wout, !bn_prefix.empty());
+        return u;
+    }
+    // A unit without parameters, emitted: kind, sources, channels, and the sizes its site sets - many leave hin / win at 0, and the
+    // plan keeps that.  relu = 0 (U_POOL alone keeps the struct's default of 1: see its sites).  The reference is good until the next emit.
+    Unit& op(UnitKind kind, int src0, int src1, int c, int hin, int win, int hout, int wout) {
+        Unit u; u.kind = kind; u.src0 = src0; u.src1 = src1; u.cout = c; u.hin = hin; u.win = win; u.hout = hout; u.wout = wout; u.relu = 0;
+        u.out = act(c, hout, wout, false);
+        U.push_back(u);
+        return U.back();
+    }
+    int gap(int src, int c, int h, int w) { return op(U_GAP, src, -1, c, h, w, 1, 1).out; }   // nn.AdaptiveAvgPool2d(1)
+    int concat(const std::vector<int>& members, int c, int h, int w) {
+        Unit& u = op(U_CONCAT, -1, -1, c, 0, 0, h, w);
+        u.members = members;
+        return u.out;
+    }
+    int maxpool(int src, int c, int h, int w) {   // nn.MaxPool2d(3, 2, 1)
+        Unit& u = op(U_POOL, src, -1, c, h, w, h / 2, w / 2);
+        u.relu = 1;
+        return u.out;
+    }
+    // standalone BatchNorm2d + activation (0 none / 1 ReLU / 2 swish), emitted
+    Unit& bn_unit(const std::string& prefix, int src, int c, int h, int w, int activation) {
+        Unit u; u.kind = U_BN; u.src0 = src; u.cin0 = c; u.cout = c; u.hin = u.hout = h; u.win = u.wout = w; u.relu = activation;
+        u.bn_idx = bn(prefix, c); u.out = act(c, h, w, false);
+        U.push_back(u);
+        return U.back();
+    }
+    // depthwise k x k convolution with `pad` zero rows / columns in front, no norm, emitted; bcast: on the single-channel network input
+    int dwconv2(const std::string& wname, int src, int c, int k, int stride, int pad, int dil, int h, int w, int bcast) {
+        Unit u; u.kind = U_DWCONV2; u.src0 = src; u.cin0 = bcast ? 1 : c; u.cout = c; u.k = k; u.stride = stride; u.dil = dil; u.pad = pad;
+        u.hin = h; u.win = w; u.hout = h / stride; u.wout = w / stride; u.bcast = bcast; u.relu = 0; u.frozen_candidate = true;
+        u.w_idx = weight(wname, {c, 1, k, k});
+        u.out = act(c, u.hout, u.wout, false);
+        return emit(u);
+    }
+    // a squeeze-excitation gate: its four tensors W1, b1, W2, b2 (returns the index of W1), and - not always right behind them - the
+    // unit on the pooled feature `src`; `activation` is what the site puts into Unit::relu (EfficientNet 2 = swish, MA-Net 0)
+    int se_tensors(const std::string& reduce, const std::string& expand, int c, int hidden) {
+        const int w = weight(reduce + ".weight", {hidden, c, 1, 1}); bias(reduce + ".bias", hidden);
+        weight(expand + ".weight", {c, hidden, 1, 1}); bias(expand + ".bias", c);
+        return w;
+    }
+    int se(int src, int c, int hidden, int widx, int activation) {
+        Unit& u = op(U_SE, src, -1, c, 0, 0, 1, 1);
+        u.cin0 = c; u.cin1 = hidden; u.w_idx = widx; u.relu = activation;
+        return u.out;
+    }
+};
+
+// activations / channels of the encoder features the decoder taps: [1] the stem at stride 2 .. [5] the deepest
+struct Features { int feat[6] = {-1, -1, -1, -1, -1, -1}, featc[6] = {0, 64, 0, 0, 0, 0}; };
+struct HeadInput { int act, c, k, up; };   // what a decoder hands to the segmentation head: its input, the head's kernel size, the upsampling behind it
+
+// dilation of encoder stage `stage` (0 .. 3 = layer1 .. layer4) under the dilating decoders (smp's replace_strides_with_dilation):
+// DeepLabV3+ (output stride 16) and PAN (encoder_dilation): the last stage with dilation 2; DeepLabV3 (output stride 8): stage 2 with 2, stage 3 with 4
+int stage_dilation(int topology, int stage) {
+    if (topology == 4 || topology == 7) return stage == 3 ? 2 : 1;
+    if (topology == 5) return stage == 2 ? 2 : (stage == 3 ? 4 : 1);
+    return 1;
+}
+
+Features encoder_efficientnet(Builder& B) {
+    // smp's EfficientNetEncoder (encoders/efficientnet.py) over efficientnet-pytorch 0.6.3's EfficientNet-b3 / b4: stem 3x3 / 2 + BN +
+    // swish; MBConv blocks = [expand 1x1 + BN + swish] depthwise k x k + BN + swish, squeeze-excitation (hidden = max(1, input
+    // filters / 4), swish), project 1x1 + BN, drop_connect(0.2 * i / blocks) + skip when the shape is kept; BatchNorm2d(momentum 0.01,
+    // eps 1e-3); Conv2dStaticSamePadding at the (even) nominal image size: (0, 1) for k = 3 and (1, 2) for k = 5 at stride 2.
+    // _conv_head / _bn1 stay in the state dict and are never run.  Registration order = execution order.
+    const vs_unet* net = B.net;
+    const int H = net->h, W = net->w;
+    Features f;
+    const bool b4 = net->encoder == 104;
+    const double width = b4 ? 1.4 : 1.2, depth = b4 ? 1.8 : 1.4;
+    auto round_filters = [&](int c) { const double x = c * width; int nw = std::max(8, (int)(x + 4) / 8 * 8); if (nw < 0.9 * x) nw += 8; return nw; };
+    auto round_repeats = [&](int r) { return (int)std::ceil(depth * r); };
+    static const int base[7][6] = {{1, 3, 1, 1, 32, 16}, {2, 3, 2, 6, 16, 24}, {2, 5, 2, 6, 24, 40}, {3, 3, 2, 6, 40, 80}, {3, 5, 1, 6, 80, 112},
+                                   {4, 5, 2, 6, 112, 192}, {1, 3, 1, 6, 192, 320}};
+    static const int ends_b3[4] = {5, 8, 18, 26}, ends_b4[4] = {6, 10, 22, 32};
+    const int* ends = b4 ? ends_b4 : ends_b3;
+    auto bn_unit = [&](const std::string& name, int src, int cch, int hh, int ww, int act) {
+        Unit& u = B.bn_unit(name, src, cch, hh, ww, act);
+        u.bn_eps = 1e-3f; u.bn_mom = 0.01f;
+        return u.out;
     };
-    // cat([nearest-x2(x), skip members...]) as ONE activation (U_UP2 + U_CONCAT): the route for boundaries the fused loader does not take
-    auto materialised_cat = [&](int x_act, int x_c, const std::vector<int>& skip_members, int skip_c) {
-        const Act xa = A[x_act];
-        Unit up; up.kind = U_UP2; up.src0 = x_act; up.cout = x_c; up.hin = xa.h; up.win = xa.w; up.hout = 2 * xa.h; up.wout = 2 * xa.w; up.relu = 0;
-        up.out = new_act(x_c, 2 * xa.h, 2 * xa.w, false);
-        U.push_back(up);
-        Unit cu; cu.kind = U_CONCAT; cu.members = {up.out};
-        for (int m : skip_members) cu.members.push_back(m);
-        cu.cout = x_c + skip_c; cu.hout = 2 * xa.h; cu.wout = 2 * xa.w; cu.relu = 0;
-        cu.out = new_act(x_c + skip_c, 2 * xa.h, 2 * xa.w, false);
-        U.push_back(cu);
-        return cu.out;
+    auto pw_conv = [&](const std::string& name, int src, int cin, int cout, int hh, int ww) {    // 1x1, no bias, no norm of its own
+        Unit u = B.conv_unit(name, "", "", src, cin, cout, 1, 1, hh, ww);
+        u.relu = 0; u.frozen_candidate = true;
+        return B.emit(u);
     };
-    // ---- encoder ----
-    int feat[6]; int featc[6] = {0, 64, 0, 0, 0, 0};          // activations / channels of the encoder features the decoder taps
-    int cur = -1, inpl = 64, ch = H / 4, cw = W / 4;
-    if (net->encoder == 103 || net->encoder == 104) {
-        // smp's EfficientNetEncoder (encoders/efficientnet.py) over efficientnet-pytorch 0.6.3's EfficientNet-b3 / b4: stem 3x3 / 2 + BN +
-        // swish; MBConv blocks = [expand 1x1 + BN + swish] depthwise k x k + BN + swish, squeeze-excitation (hidden = max(1, input
-        // filters / 4), swish), project 1x1 + BN, drop_connect(0.2 * i / blocks) + skip when the shape is kept; BatchNorm2d(momentum 0.01,
-        // eps 1e-3); Conv2dStaticSamePadding at the (even) nominal image size: (0, 1) for k = 3 and (1, 2) for k = 5 at stride 2.
-        // _conv_head / _bn1 stay in the state dict and are never run.  Registration order = execution order.
-        const bool b4 = net->encoder == 104;
-        const double width = b4 ? 1.4 : 1.2, depth = b4 ? 1.8 : 1.4;
-        auto round_filters = [&](int f) { const double x = f * width; int nw = std::max(8, (int)(x + 4) / 8 * 8); if (nw < 0.9 * x) nw += 8; return nw; };
-        auto round_repeats = [&](int r) { return (int)std::ceil(depth * r); };
-        static const int base[7][6] = {{1, 3, 1, 1, 32, 16}, {2, 3, 2, 6, 16, 24}, {2, 5, 2, 6, 24, 40}, {3, 3, 2, 6, 40, 80}, {3, 5, 1, 6, 80, 112},
-                                       {4, 5, 2, 6, 112, 192}, {1, 3, 1, 6, 192, 320}};
-        static const int ends_b3[4] = {5, 8, 18, 26}, ends_b4[4] = {6, 10, 22, 32};
-        const int* ends = b4 ? ends_b4 : ends_b3;
-        auto bn_unit = [&](const std::string& name, int src, int cch, int hh, int ww, int act) {
-            Unit u; u.kind = U_BN; u.src0 = src; u.cin0 = cch; u.cout = cch; u.hin = u.hout = hh; u.win = u.wout = ww; u.relu = act;
-            u.bn_eps = 1e-3f; u.bn_mom = 0.01f; u.bn_idx = add_bn(L, name, cch); u.out = new_act(cch, hh, ww, false);
-            U.push_back(u);
-            return u.out;
-        };
-        auto pw_conv = [&](const std::string& name, int src, int cin, int cout, int hh, int ww) {    // 1x1, no bias, no norm of its own
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = 1; u.pad = 0; u.stride = 1; u.hin = u.hout = hh; u.win = u.wout = ww;
-            u.relu = 0; u.frozen_candidate = true; u.w_idx = (int)L.tensors.size(); add_tensor(L, name, {cout, cin, 1, 1}, 0);
-            u.out = new_act(cout, hh, ww, false);
-            U.push_back(u);
-            return u.out;
-        };
-        auto dw_conv = [&](const std::string& name, int src, int cch, int k, int st, int hh, int ww, int bcast, int dil = 1) {
-            Unit u; u.kind = U_DWCONV2; u.src0 = src; u.cin0 = bcast ? 1 : cch; u.cout = cch; u.k = k; u.stride = st; u.dil = dil;
-            u.pad = dil > 1 ? (k / 2) * dil : (st == 2 ? (k == 3 ? 0 : 1) : k / 2);
-            u.hin = hh; u.win = ww; u.hout = hh / st; u.wout = ww / st; u.bcast = bcast; u.relu = 0; u.frozen_candidate = true;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, name, {cch, 1, k, k}, 0);
-            u.out = new_act(cch, hh / st, ww / st, false);
-            U.push_back(u);
-            return u.out;
-        };
-        const int stem_c = round_filters(32);
-        cur = dw_conv("encoder._conv_stem.weight", -1, stem_c, 3, 2, H, W, 1);
-        cur = bn_unit("encoder._bn0", cur, stem_c, H / 2, W / 2, 2);
-        feat[1] = cur; featc[1] = stem_c;
-        ch = H / 2; cw = W / 2;
-        int nblocks = 0;
-        for (auto& b : base) nblocks += round_repeats(b[0]);
-        int bi = 0, stage = 0;
-        for (auto& b : base) {
-            const int k = b[1], e = b[3], o = round_filters(b[5]);
-            for (int j = 0; j < round_repeats(b[0]); ++j, ++bi) {
-                // DeepLabV3+ (output stride 16): smp's replace_strides_with_dilation on the last stage (blocks[ends[2]:]) - every
-                // convolution stride 1, dilation 2, padding (k / 2) * 2, the static padding dropped ("Kostyl for EfficientNet")
-                // DeepLabV3 (output stride 8): stages 4 and 5 (blocks[ends[1]:ends[2]], blocks[ends[2]:]) with dilation 2 and 4
-                // PAN (encoder_dilation): the last stage with dilation 2, as DeepLabV3+
-                const int stage_dil = (net->topology == 4 || net->topology == 7) ? (bi >= ends[2] ? 2 : 1)
-                                      : net->topology == 5 ? (bi >= ends[2] ? 4 : (bi >= ends[1] ? 2 : 1)) : 1;
-                const bool dilated = stage_dil > 1;
-                const int st = (j == 0 && !dilated) ? b[2] : 1, inp = j == 0 ? round_filters(b[4]) : o, oup = inp * e;
-                const std::string pre = "encoder._blocks." + std::to_string(bi);
-                const int x_in = cur;
-                int t = cur;
-                if (e != 1) {
-                    t = pw_conv(pre + "._expand_conv.weight", t, inp, oup, ch, cw);
-                    t = bn_unit(pre + "._bn0", t, oup, ch, cw, 2);
-                }
-                t = dw_conv(pre + "._depthwise_conv.weight", t, oup, k, st, ch, cw, 0, stage_dil);
-                const int oh = ch / st, ow = cw / st;
-                t = bn_unit(pre + "._bn1", t, oup, oh, ow, 2);
-                const int R = std::max(1, inp / 4);
-                Unit gp; gp.kind = U_GAP; gp.src0 = t; gp.cout = oup; gp.hin = oh; gp.win = ow; gp.hout = 1; gp.wout = 1; gp.relu = 0;
-                gp.out = new_act(oup, 1, 1, false);
-                U.push_back(gp);
-                Unit se; se.kind = U_SE; se.src0 = gp.out; se.cout = oup; se.cin0 = oup; se.cin1 = R; se.hout = 1; se.wout = 1; se.relu = 2;
-                se.w_idx = (int)L.tensors.size();
-                add_tensor(L, pre + "._se_reduce.weight", {R, oup, 1, 1}, 0); add_tensor(L, pre + "._se_reduce.bias", {R}, 3);
-                add_tensor(L, pre + "._se_expand.weight", {oup, R, 1, 1}, 0); add_tensor(L, pre + "._se_expand.bias", {oup}, 3);
-                se.out = new_act(oup, 1, 1, false);
-                U.push_back(se);
-                Unit cg; cg.kind = U_CGATE; cg.src0 = t; cg.src1 = se.out; cg.cout = oup; cg.hout = oh; cg.wout = ow; cg.relu = 0;
-                cg.out = new_act(oup, oh, ow, false);
-                U.push_back(cg);
-                t = pw_conv(pre + "._project_conv.weight", cg.out, oup, o, oh, ow);
-                t = bn_unit(pre + "._bn2", t, o, oh, ow, 0);
-                if (st == 1 && inp == o) {
-                    Unit da; da.kind = U_DROPADD; da.src0 = t; da.src1 = x_in; da.cout = o; da.hin = da.hout = oh; da.win = da.wout = ow; da.relu = 0;
-                    da.drop_p = 0.2f * (float)bi / (float)nblocks; da.salt = bi;
-                    da.out = new_act(o, oh, ow, false);
-                    U.push_back(da);
-                    t = da.out;
-                }
-                cur = t; ch = oh; cw = ow; inpl = o;
-                if (stage < 4 && bi + 1 == ends[stage]) { feat[stage + 2] = cur; featc[stage + 2] = o; ++stage; }
+    auto dw_conv = [&](const std::string& name, int src, int cch, int k, int st, int hh, int ww, int bcast, int dil = 1) {
+        const int pad = dil > 1 ? (k / 2) * dil : (st == 2 ? (k == 3 ? 0 : 1) : k / 2);
+        return B.dwconv2(name, src, cch, k, st, pad, dil, hh, ww, bcast);
+    };
+    const int stem_c = round_filters(32);
+    int cur = dw_conv("encoder._conv_stem.weight", -1, stem_c, 3, 2, H, W, 1);
+    cur = bn_unit("encoder._bn0", cur, stem_c, H / 2, W / 2, 2);
+    f.feat[1] = cur; f.featc[1] = stem_c;
+    int ch = H / 2, cw = W / 2, inpl = 64;
+    int nblocks = 0;
+    for (auto& b : base) nblocks += round_repeats(b[0]);
+    int bi = 0, stage = 0;
+    for (auto& b : base) {
+        const int k = b[1], e = b[3], o = round_filters(b[5]);
+        for (int j = 0; j < round_repeats(b[0]); ++j, ++bi) {
+            // DeepLabV3+ (output stride 16): smp's replace_strides_with_dilation on the last stage (blocks[ends[2]:]) - every
+            // convolution stride 1, dilation 2, padding (k / 2) * 2, the static padding dropped ("Kostyl for EfficientNet")
+            // DeepLabV3 (output stride 8): stages 4 and 5 (blocks[ends[1]:ends[2]], blocks[ends[2]:]) with dilation 2 and 4
+            // PAN (encoder_dilation): the last stage with dilation 2, as DeepLabV3+
+            const int stage_dil = stage_dilation(net->topology, bi >= ends[2] ? 3 : (bi >= ends[1] ? 2 : 1));
+            const bool dilated = stage_dil > 1;
+            const int st = (j == 0 && !dilated) ? b[2] : 1, inp = j == 0 ? round_filters(b[4]) : o, oup = inp * e;
+            const std::string pre = "encoder._blocks." + std::to_string(bi);
+            const int x_in = cur;
+            int t = cur;
+            if (e != 1) {
+                t = pw_conv(pre + "._expand_conv.weight", t, inp, oup, ch, cw);
+                t = bn_unit(pre + "._bn0", t, oup, ch, cw, 2);
             }
-        }
-        add_tensor(L, "encoder._conv_head.weight", {round_filters(1280), inpl, 1, 1}, 0);     // registered by efficientnet-pytorch, never run
-        add_bn(L, "encoder._bn1", round_filters(1280));
-    } else if (net->encoder == 150 || net->encoder == 201) {
-        // smp's timm-resnest50d / timm-resnest101e (timm 0.4.12 ResNet(ResNestBottleneck, stem_type 'deep', avg_down, radix 2, avd)):
-        // deep stem conv1 = [3x3 / 2 (1 -> sw) BN ReLU, 3x3 (sw -> sw) BN ReLU, 3x3 (sw -> 2 sw)], bn1, ReLU, MaxPool(3, 2, 1); blocks = conv1 1x1 +
-        // bn1 + ReLU, conv2 = SplitAttnConv2d (3x3 onto 2 C channels in two groups + bn0 + ReLU; the splits summed and average-pooled;
-        // fc1 (bias) + bn1 + ReLU; fc2 (bias); RadixSoftmax; the attention-weighted sum of the splits), avd_last = AvgPool2d(3, 2, 1) in
-        // the stride-2 blocks, conv3 1x1 + bn3 (+ shortcut, ReLU); shortcut = [AvgPool2d(2, 2)] + 1x1 + BN.  The reference's freeze
-        // predicate ("encoder" and "conv" in the name) also takes conv2.bn0 / conv2.fc1 / conv2.bn1 / conv2.fc2 and the stem's BatchNorms.
-        const bool e101 = net->encoder == 201;
-        const int sw = e101 ? 64 : 32;
-        const int blocks_n[4] = {3, 4, e101 ? 23 : 6, 3};
-        auto conv_bn = [&](const std::string& wname, const std::string& bnname, int src, int cin, int cout, int k, int hh, int ww, int relu,
-                           bool frozen, bool bn_frozen, int two_groups = 0) {
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2; u.stride = 1; u.g2 = two_groups;
-            u.hin = hh; u.win = ww; u.hout = hh; u.wout = ww; u.relu = relu; u.frozen_candidate = frozen; u.aux_frozen = bn_frozen;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, wname, {cout, two_groups ? cin / 2 : cin, k, k}, 0);
-            u.bn_idx = add_bn(L, bnname, cout);
-            u.out = new_act(cout, hh, ww, true);
-            return u;
-        };
-        {   // deep stem
-            Unit d; d.kind = U_DWCONV2; d.src0 = -1; d.cin0 = 1; d.cout = sw; d.k = 3; d.stride = 2; d.pad = 1; d.bcast = 1; d.relu = 0; d.frozen_candidate = true;
-            d.hin = H; d.win = W; d.hout = H / 2; d.wout = W / 2;
-            d.w_idx = (int)L.tensors.size(); add_tensor(L, "encoder.conv1.0.weight", {sw, 1, 3, 3}, 0);
-            d.out = new_act(sw, H / 2, W / 2, false);
-            U.push_back(d);
-            Unit b; b.kind = U_BN; b.src0 = d.out; b.cin0 = sw; b.cout = sw; b.hin = b.hout = H / 2; b.win = b.wout = W / 2; b.relu = 1; b.aux_frozen = true;
-            b.bn_idx = add_bn(L, "encoder.conv1.1", sw); b.out = new_act(sw, H / 2, W / 2, false);
-            U.push_back(b);
-            Unit c3 = conv_bn("encoder.conv1.3.weight", "encoder.conv1.4", b.out, sw, sw, 3, H / 2, W / 2, 1, true, true);
-            U.push_back(c3);
-            Unit c6 = conv_bn("encoder.conv1.6.weight", "encoder.bn1", c3.out, sw, 2 * sw, 3, H / 2, W / 2, 1, true, false);
-            U.push_back(c6);
-            feat[1] = c6.out; featc[1] = 2 * sw;
-            Unit pool; pool.kind = U_POOL; pool.src0 = c6.out; pool.cout = 2 * sw; pool.hin = H / 2; pool.win = W / 2;
-            pool.hout = H / 4; pool.wout = W / 4; pool.out = new_act(2 * sw, H / 4, W / 4, false);
-            U.push_back(pool);
-            cur = pool.out; inpl = 2 * sw; ch = H / 4; cw = W / 4;
-        }
-        const int planes_r[4] = {64, 128, 256, 512};
-        for (int l = 0; l < 4; ++l) {
-            for (int bidx = 0; bidx < blocks_n[l]; ++bidx) {
-                const std::string pre = "encoder.layer" + std::to_string(l + 1) + "." + std::to_string(bidx);
-                const int stride = (bidx == 0 && l > 0) ? 2 : 1, C = planes_r[l], outc = 4 * C, A = std::max(C * 2 / 4, 32);
-                const int oh = ch / stride, ow = cw / stride;
-                const int x_in = cur;
-                Unit u1 = conv_bn(pre + ".conv1.weight", pre + ".bn1", cur, inpl, C, 1, ch, cw, 1, true, false);
-                U.push_back(u1);
-                Unit u2 = conv_bn(pre + ".conv2.conv.weight", pre + ".conv2.bn0", u1.out, C, 2 * C, 3, ch, cw, 1, true, true, 1);   // [2 C][C / 2][3][3]
-                U.push_back(u2);
-                Unit gp; gp.kind = U_GAP; gp.src0 = u2.out; gp.cout = 2 * C; gp.hin = ch; gp.win = cw; gp.hout = 1; gp.wout = 1; gp.relu = 0;
-                gp.out = new_act(2 * C, 1, 1, false);
-                U.push_back(gp);
-                Unit fd; fd.kind = U_FOLD2; fd.src0 = gp.out; fd.cout = C; fd.hin = fd.hout = 1; fd.win = fd.wout = 1; fd.relu = 0;
-                fd.out = new_act(C, 1, 1, false);
-                U.push_back(fd);
-                Unit f1; f1.kind = U_CONV; f1.src0 = fd.out; f1.cin0 = C; f1.cout = A; f1.k = 1; f1.pad = 0; f1.hin = f1.hout = 1; f1.win = f1.wout = 1; f1.relu = 1;
-                f1.frozen_candidate = true; f1.aux_frozen = true;
-                f1.w_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv2.fc1.weight", {A, C, 1, 1}, 0);
-                f1.bias_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv2.fc1.bias", {A}, 3);
-                f1.bn_idx = add_bn(L, pre + ".conv2.bn1", A);
-                f1.out = new_act(A, 1, 1, true);
-                U.push_back(f1);
-                Unit f2; f2.kind = U_CONV; f2.src0 = f1.out; f2.cin0 = A; f2.cout = 2 * C; f2.k = 1; f2.pad = 0; f2.hin = f2.hout = 1; f2.win = f2.wout = 1; f2.relu = 0;
-                f2.frozen_candidate = true; f2.aux_frozen = true;
-                f2.w_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv2.fc2.weight", {2 * C, A, 1, 1}, 0);
-                f2.bias_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv2.fc2.bias", {2 * C}, 3);
-                f2.out = new_act(2 * C, 1, 1, false);
-                U.push_back(f2);
-                Unit rs; rs.kind = U_RSOFTMAX; rs.src0 = f2.out; rs.cout = 2 * C; rs.hin = rs.hout = 1; rs.win = rs.wout = 1; rs.relu = 0;
-                rs.out = new_act(2 * C, 1, 1, false);
-                U.push_back(rs);
-                Unit fo; fo.kind = U_RADIXSUM; fo.src0 = u2.out; fo.src1 = rs.out; fo.cout = C; fo.hin = fo.hout = ch; fo.win = fo.wout = cw; fo.relu = 0;
-                fo.out = new_act(C, ch, cw, false);
-                U.push_back(fo);
-                int t = fo.out;
-                if (stride == 2) {      // avd_last = nn.AvgPool2d(3, 2, padding=1): the padding zeros count (count_include_pad)
-                    Unit ap; ap.kind = U_AVGPOOL; ap.src0 = t; ap.cout = C; ap.k = 3; ap.stride = 2; ap.pad = 1; ap.pool_w = 1.f / 9.f; ap.relu = 0;
-                    ap.hin = ch; ap.win = cw; ap.hout = oh; ap.wout = ow; ap.out = new_act(C, oh, ow, false);
-                    U.push_back(ap);
-                    t = ap.out;
-                }
-                Unit u3 = conv_bn(pre + ".conv3.weight", pre + ".bn3", t, C, outc, 1, oh, ow, 1, true, false);
-                if (bidx == 0) {        // downsample_avg: [AvgPool2d(2, 2, ceil_mode, count_include_pad=False)] + 1x1 convolution + BatchNorm
-                    int ds = x_in;
-                    if (stride == 2) {
-                        Unit ap; ap.kind = U_AVGPOOL; ap.src0 = x_in; ap.cout = inpl; ap.k = 2; ap.stride = 2; ap.pad = 0; ap.pool_w = 0.25f; ap.relu = 0;
-                        ap.hin = ch; ap.win = cw; ap.hout = oh; ap.wout = ow; ap.out = new_act(inpl, oh, ow, false);
-                        U.push_back(ap);
-                        ds = ap.out;
-                    }
-                    Unit ud = conv_bn(pre + ".downsample.1.weight", pre + ".downsample.2", ds, inpl, outc, 1, oh, ow, 0, false, false);
-                    // state-dict order: conv3, bn3, then downsample.* - the tensors of u3 were registered first (conv_bn above)
-                    U.push_back(ud);
-                    u3.res = ud.out;
-                } else {
-                    u3.res = x_in;
-                }
-                U.push_back(u3);
-                cur = u3.out; inpl = outc; ch = oh; cw = ow;
+            t = dw_conv(pre + "._depthwise_conv.weight", t, oup, k, st, ch, cw, 0, stage_dil);
+            const int oh = ch / st, ow = cw / st;
+            t = bn_unit(pre + "._bn1", t, oup, oh, ow, 2);
+            const int R = std::max(1, inp / 4);
+            const int pooled = B.gap(t, oup, oh, ow);
+            const int gate = B.se(pooled, oup, R, B.se_tensors(pre + "._se_reduce", pre + "._se_expand", oup, R), 2);
+            const int gated = B.op(U_CGATE, t, gate, oup, 0, 0, oh, ow).out;
+            t = pw_conv(pre + "._project_conv.weight", gated, oup, o, oh, ow);
+            t = bn_unit(pre + "._bn2", t, o, oh, ow, 0);
+            if (st == 1 && inp == o) {
+                Unit& da = B.op(U_DROPADD, t, x_in, o, oh, ow, oh, ow);
+                da.drop_p = 0.2f * (float)bi / (float)nblocks; da.salt = bi;
+                t = da.out;
             }
-            feat[l + 2] = cur; featc[l + 2] = inpl;
+            cur = t; ch = oh; cw = ow; inpl = o;
+            if (stage < 4 && bi + 1 == ends[stage]) { f.feat[stage + 2] = cur; f.featc[stage + 2] = o; ++stage; }
         }
-    } else {
-    add_tensor(L, "encoder.conv1.weight", {64, 1, 7, 7}, 0);
+    }
+    B.weight("encoder._conv_head.weight", {round_filters(1280), inpl, 1, 1});     // registered by efficientnet-pytorch, never run
+    B.bn("encoder._bn1", round_filters(1280));
+    return f;
+}
+
+Features encoder_resnest(Builder& B) {
+    // smp's timm-resnest50d / timm-resnest101e (timm 0.4.12 ResNet(ResNestBottleneck, stem_type 'deep', avg_down, radix 2, avd)):
+    // deep stem conv1 = [3x3 / 2 (1 -> sw) BN ReLU, 3x3 (sw -> sw) BN ReLU, 3x3 (sw -> 2 sw)], bn1, ReLU, MaxPool(3, 2, 1); blocks = conv1 1x1 +
+    // bn1 + ReLU, conv2 = SplitAttnConv2d (3x3 onto 2 C channels in two groups + bn0 + ReLU; the splits summed and average-pooled;
+    // fc1 (bias) + bn1 + ReLU; fc2 (bias); RadixSoftmax; the attention-weighted sum of the splits), avd_last = AvgPool2d(3, 2, 1) in
+    // the stride-2 blocks, conv3 1x1 + bn3 (+ shortcut, ReLU); shortcut = [AvgPool2d(2, 2)] + 1x1 + BN.  The reference's freeze
+    // predicate ("encoder" and "conv" in the name) also takes conv2.bn0 / conv2.fc1 / conv2.bn1 / conv2.fc2 and the stem's BatchNorms.
+    const vs_unet* net = B.net;
+    const int H = net->h, W = net->w;
+    Features f;
+    const bool e101 = net->encoder == 201;
+    const int sw = e101 ? 64 : 32;
+    const int blocks_n[4] = {3, 4, e101 ? 23 : 6, 3};
+    // (described, not emitted: conv3 is described - tensors registered, output allocated - BEFORE the shortcut that runs ahead of it)
+    auto conv_bn = [&](const std::string& wname, const std::string& bias, const std::string& bnname, int src, int cin, int cout, int k, int hh, int ww,
+                       int relu, bool frozen, bool aux_frozen, int two_groups = 0) {
+        Unit u = B.conv_unit(wname, bias, bnname, src, cin, cout, k, 1, hh, ww, two_groups ? cin / 2 : 0);
+        u.g2 = two_groups; u.relu = relu; u.frozen_candidate = frozen; u.aux_frozen = aux_frozen;
+        return u;
+    };
+    auto avgpool = [&](int src, int c, int k, int pad, int hh, int ww) {
+        Unit& ap = B.op(U_AVGPOOL, src, -1, c, hh, ww, hh / 2, ww / 2);
+        ap.k = k; ap.stride = 2; ap.pad = pad; ap.pool_w = 1.f / (float)(k * k);
+        return ap.out;
+    };
+    // deep stem
+    int cur = B.dwconv2("encoder.conv1.0.weight", -1, sw, 3, 2, 1, 1, H, W, 1);
+    Unit& b = B.bn_unit("encoder.conv1.1", cur, sw, H / 2, W / 2, 1);
+    b.aux_frozen = true;
+    cur = B.emit(conv_bn("encoder.conv1.3.weight", "", "encoder.conv1.4", b.out, sw, sw, 3, H / 2, W / 2, 1, true, true));
+    cur = B.emit(conv_bn("encoder.conv1.6.weight", "", "encoder.bn1", cur, sw, 2 * sw, 3, H / 2, W / 2, 1, true, false));
+    f.feat[1] = cur; f.featc[1] = 2 * sw;
+    cur = B.maxpool(cur, 2 * sw, H / 2, W / 2);
+    int inpl = 2 * sw, ch = H / 4, cw = W / 4;
+    const int planes_r[4] = {64, 128, 256, 512};
+    for (int l = 0; l < 4; ++l) {
+        for (int bidx = 0; bidx < blocks_n[l]; ++bidx) {
+            const std::string pre = "encoder.layer" + std::to_string(l + 1) + "." + std::to_string(bidx);
+            const int stride = (bidx == 0 && l > 0) ? 2 : 1, C = planes_r[l], outc = 4 * C, hidden = std::max(C * 2 / 4, 32);
+            const int oh = ch / stride, ow = cw / stride;
+            const int x_in = cur;
+            const int u1 = B.emit(conv_bn(pre + ".conv1.weight", "", pre + ".bn1", cur, inpl, C, 1, ch, cw, 1, true, false));
+            // (conv2.conv's weight: [2 C][C / 2][3][3])
+            const int u2 = B.emit(conv_bn(pre + ".conv2.conv.weight", "", pre + ".conv2.bn0", u1, C, 2 * C, 3, ch, cw, 1, true, true, 1));
+            const int pooled = B.gap(u2, 2 * C, ch, cw);
+            const int folded = B.op(U_FOLD2, pooled, -1, C, 1, 1, 1, 1).out;
+            const int f1 = B.emit(conv_bn(pre + ".conv2.fc1.weight", pre + ".conv2.fc1.bias", pre + ".conv2.bn1", folded, C, hidden, 1, 1, 1, 1, true, true));
+            const int f2 = B.emit(conv_bn(pre + ".conv2.fc2.weight", pre + ".conv2.fc2.bias", "", f1, hidden, 2 * C, 1, 1, 1, 0, true, true));
+            const int attn = B.op(U_RSOFTMAX, f2, -1, 2 * C, 1, 1, 1, 1).out;
+            int t = B.op(U_RADIXSUM, u2, attn, C, ch, cw, ch, cw).out;
+            if (stride == 2) t = avgpool(t, C, 3, 1, ch, cw);     // avd_last = nn.AvgPool2d(3, 2, padding=1): the padding zeros count (count_include_pad)
+            Unit u3 = conv_bn(pre + ".conv3.weight", "", pre + ".bn3", t, C, outc, 1, oh, ow, 1, true, false);
+            if (bidx == 0) {        // downsample_avg: [AvgPool2d(2, 2, ceil_mode, count_include_pad=False)] + 1x1 convolution + BatchNorm
+                const int ds = stride == 2 ? avgpool(x_in, inpl, 2, 0, ch, cw) : x_in;
+                // state-dict order: conv3, bn3, then downsample.* - the tensors of u3 were registered first (conv_bn above)
+                u3.res = B.emit(conv_bn(pre + ".downsample.1.weight", "", pre + ".downsample.2", ds, inpl, outc, 1, oh, ow, 0, false, false));
+            } else {
+                u3.res = x_in;
+            }
+            cur = B.emit(u3); inpl = outc; ch = oh; cw = ow;
+        }
+        f.feat[l + 2] = cur; f.featc[l + 2] = inpl;
+    }
+    return f;
+}
+
+Features encoder_resnet(Builder& B) {
+    // torchvision's ResNet behind smp's resnet18 / resnet34 / resnet50 / resnext50_32x4d with a single input channel
+    const vs_unet* net = B.net;
+    const int H = net->h, W = net->w;
+    Features f;
     Unit stem; stem.kind = U_STEM; stem.cout = 64; stem.k = 7; stem.stride = 2; stem.pad = 3;
-    stem.hin = H; stem.win = W; stem.hout = H / 2; stem.wout = W / 2;
-    stem.w_idx = 0; stem.bn_idx = add_bn(L, "encoder.bn1", 64);
-    stem.out = new_act(64, H / 2, W / 2, true); stem.frozen_candidate = true;
-    U.push_back(stem);
-    feat[1] = stem.out;
-    Unit pool; pool.kind = U_POOL; pool.src0 = stem.out; pool.cout = 64; pool.hin = H / 2; pool.win = W / 2;
-    pool.hout = H / 4; pool.wout = W / 4; pool.out = new_act(64, H / 4, W / 4, false);
-    U.push_back(pool);
-    cur = pool.out; inpl = 64; ch = H / 4; cw = W / 4;
+    stem.hin = H; stem.win = W; stem.hout = H / 2; stem.wout = W / 2; stem.frozen_candidate = true;
+    stem.w_idx = B.weight("encoder.conv1.weight", {64, 1, 7, 7});
+    B.attach_bn(stem, "encoder.bn1");
+    stem.out = B.act(64, H / 2, W / 2, true);
+    f.feat[1] = B.emit(stem);
+    int cur = B.maxpool(stem.out, 64, H / 2, W / 2), inpl = 64, ch = H / 4, cw = W / 4;
     const int planes[4] = {64, 128, 256, 512};
     const int blocks18[4] = {2, 2, 2, 2}, blocks34[4] = {3, 4, 6, 3};   // resnet50 uses the resnet34 block counts
     const int* blocks = net->encoder == 18 ? blocks18 : blocks34;
@@ -499,536 +537,405 @@ int build(vs_unet* net) {
             // convolution of the stage gets stride 1, and the 3x3 ones dilation 2 / padding 2
             // DeepLabV3 (output stride 8): layer3 with dilation 2, layer4 with dilation 4
             // PAN (encoder_dilation=True): layer4 with dilation 2, as DeepLabV3+
-            const int stage_dil = (net->topology == 4 || net->topology == 7) ? (l == 3 ? 2 : 1) : (net->topology == 5 ? (l == 2 ? 2 : (l == 3 ? 4 : 1)) : 1);
+            const int stage_dil = stage_dilation(net->topology, l);
             const bool dilated = stage_dil > 1;
             const int stride = (b == 0 && l > 0 && !dilated) ? 2 : 1;
             const int oh = ch / stride, ow = cw / stride, pl = planes[l], outc = pl * expansion;
-            auto conv_unit = [&](const std::string& name, const std::string& bn, int src, int cin, int cout, int k, int st, int hi, int wi,
-                                 bool frozen, int cg) {
-                Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2; u.stride = st;
-                u.hin = hi; u.win = wi; u.hout = hi / st; u.wout = wi / st; u.frozen_candidate = frozen; u.cg = cg;
+            auto conv_bn = [&](const std::string& name, const std::string& bn, int src, int cin, int cout, int k, int st, int hi, int wi, bool frozen, int cg) {
+                Unit u = B.conv_unit(name, "", bn, src, cin, cout, k, st, hi, wi, cg);
+                u.frozen_candidate = frozen; u.cg = cg;
                 if (dilated && k == 3) { u.dil = stage_dil; u.pad = stage_dil; }
-                u.w_idx = (int)L.tensors.size(); add_tensor(L, name, {cout, cg ? cg : cin, k, k}, 0);
-                u.bn_idx = add_bn(L, bn, cout);
-                u.out = new_act(cout, hi / st, wi / st, true);
                 return u;
             };
             // the block's convolutions in torchvision's registration order (= state_dict order): conv1 bn1 conv2 bn2 [conv3 bn3]
             // [downsample.0 downsample.1].  BasicBlock: 3x3 (stride) - 3x3; Bottleneck (v1.5): 1x1 - 3x3 (stride) - 1x1 (x4).
+            // All of them are described - and their outputs allocated - before the first is emitted; the downsample comes after.
             std::vector<Unit> us;
             if (!bottleneck) {
-                us.push_back(conv_unit(pre + ".conv1.weight", pre + ".bn1", cur, inpl, pl, 3, stride, ch, cw, true, 0));
-                us.push_back(conv_unit(pre + ".conv2.weight", pre + ".bn2", us[0].out, pl, pl, 3, 1, oh, ow, true, 0));
+                us.push_back(conv_bn(pre + ".conv1.weight", pre + ".bn1", cur, inpl, pl, 3, stride, ch, cw, true, 0));
+                us.push_back(conv_bn(pre + ".conv2.weight", pre + ".bn2", us[0].out, pl, pl, 3, 1, oh, ow, true, 0));
             } else {
                 const int width = groups > 1 ? pl * 2 : pl;
-                us.push_back(conv_unit(pre + ".conv1.weight", pre + ".bn1", cur, inpl, width, 1, 1, ch, cw, true, 0));
-                us.push_back(conv_unit(pre + ".conv2.weight", pre + ".bn2", us[0].out, width, width, 3, stride, ch, cw, true,
-                                       groups > 1 ? width / groups : 0));
-                us.push_back(conv_unit(pre + ".conv3.weight", pre + ".bn3", us[1].out, width, outc, 1, 1, oh, ow, true, 0));
+                us.push_back(conv_bn(pre + ".conv1.weight", pre + ".bn1", cur, inpl, width, 1, 1, ch, cw, true, 0));
+                us.push_back(conv_bn(pre + ".conv2.weight", pre + ".bn2", us[0].out, width, width, 3, stride, ch, cw, true,
+                                     groups > 1 ? width / groups : 0));
+                us.push_back(conv_bn(pre + ".conv3.weight", pre + ".bn3", us[1].out, width, outc, 1, 1, oh, ow, true, 0));
             }
             Unit& last = us.back();
-            for (size_t q = 0; q + 1 < us.size(); ++q) U.push_back(us[q]);
+            for (size_t q = 0; q + 1 < us.size(); ++q) B.emit(us[q]);
             if (stride != 1 || inpl != outc || (dilated && b == 0)) {   // "downsample" lacks "conv" in its name: not frozen by the reference's predicate
-                Unit ud = conv_unit(pre + ".downsample.0.weight", pre + ".downsample.1", cur, inpl, outc, 1, stride, ch, cw, false, 0);
+                Unit ud = conv_bn(pre + ".downsample.0.weight", pre + ".downsample.1", cur, inpl, outc, 1, stride, ch, cw, false, 0);
                 ud.relu = 0;
-                U.push_back(ud);
-                last.res = ud.out;
+                last.res = B.emit(ud);
             } else {
                 last.res = cur;
             }
-            U.push_back(last);
-            cur = last.out; inpl = outc; ch = oh; cw = ow;
+            cur = B.emit(last); inpl = outc; ch = oh; cw = ow;
         }
-        feat[l + 2] = cur;
-        featc[l + 2] = inpl;
+        f.feat[l + 2] = cur;
+        f.featc[l + 2] = inpl;
     }
+    return f;
+}
+
+// ---- decoders ----
+// smp's DecoderBlock on cat(nearest-x2(x), skips): Conv3x3 + BN + ReLU twice.  Its tensors, in state-dict order ..
+struct DecoderBlockTensors { int w1, bn1, w2, bn2; };
+DecoderBlockTensors decoder_block_tensors(Builder& B, const std::string& pre, int cin, int cout) {
+    DecoderBlockTensors t;
+    t.w1 = B.weight(pre + ".conv1.0.weight", {cout, cin, 3, 3}); t.bn1 = B.bn(pre + ".conv1.1", cout);
+    t.w2 = B.weight(pre + ".conv2.0.weight", {cout, cout, 3, 3}); t.bn2 = B.bn(pre + ".conv2.1", cout);
+    return t;
+}
+// .. and its units.  conv1 reads up(x) ++ skip through its loader (up0; `skips` = at most ONE activation of skip_c channels, already
+// concatenated where there were several) when the boundary x_c is a multiple of 32 channels; where it is not (EfficientNet features of
+// 136 / 56 / 48 channels) cat([nearest-x2(x), skips...]) is materialised as ONE activation (U_UP2 + U_CONCAT) and conv1 reads that.
+// conv1_act_first: conv1's output is allocated before the materialised concatenation's two activations (MA-Net describes conv1
+// first), not after them (U-Net++).  Returns conv2's output.
+int decoder_block(Builder& B, const DecoderBlockTensors& t, int x_act, int x_c, const std::vector<int>& skips, int skip_c, int cout,
+                  bool conv1_act_first = false) {
+    const int oh = 2 * B.A[x_act].h, ow = 2 * B.A[x_act].w;
+    Unit u1 = Builder::conv(x_act, x_c + skip_c, cout, 3, 1, oh, ow);
+    u1.w_idx = t.w1; u1.bn_idx = t.bn1;
+    if (conv1_act_first) u1.out = B.act(cout, oh, ow, true);
+    if (!skips.empty() && x_c % 32 != 0) {
+        const int up = B.op(U_UP2, x_act, -1, x_c, oh / 2, ow / 2, oh, ow).out;
+        std::vector<int> members = {up};
+        members.insert(members.end(), skips.begin(), skips.end());
+        u1.src0 = B.concat(members, x_c + skip_c, oh, ow);
+    } else {
+        u1.up0 = 1; u1.cin0 = x_c; u1.cin1 = skip_c; u1.src1 = skips.empty() ? -1 : skips[0];
     }
-    // ---- decoder ----
-    const int dec[5] = {256, 128, 64, 32, 16};
-    const int skipc[5] = {featc[4], featc[3], featc[2], featc[1], 0};
-    int xin = feat[5], xc = featc[5];
-    if (net->topology >= 2) {
-        // (built below, next to the head)
-    } else if (net->topology == 0) {
+    if (!conv1_act_first) u1.out = B.act(cout, oh, ow, true);
+    Unit u2 = Builder::conv(u1.out, cout, cout, 3, 1, oh, ow);
+    u2.w_idx = t.w2; u2.bn_idx = t.bn2;
+    u2.out = B.act(cout, oh, ow, true);
+    B.emit(u1);
+    return B.emit(u2);
+}
+const int kDecoderChannels[5] = {256, 128, 64, 32, 16};   // smp's default decoder_channels
+
+HeadInput decoder_unet(Builder& B, const Features& f) {
+    const int* dec = kDecoderChannels;
+    int x = f.feat[5], xc = f.featc[5];
+    for (int i = 0; i < 5; ++i) {
+        const int skip_c = i < 4 ? f.featc[4 - i] : 0;
+        const DecoderBlockTensors t = decoder_block_tensors(B, "decoder.blocks." + std::to_string(i), xc + skip_c, dec[i]);
+        x = decoder_block(B, t, x, xc, skip_c ? std::vector<int>{f.feat[4 - i]} : std::vector<int>{}, skip_c, dec[i]);
+        xc = dec[i];
+    }
+    return {x, xc, 3, 1};
+}
+
+HeadInput decoder_unetplusplus(Builder& B, const Features& f) {
+    // smp.UnetPlusPlusDecoder (decoders/unetplusplus/decoder.py of segmentation-models-pytorch 0.2.1, restated):
+    // features reversed, deepest first: f[0] = layer4 .. f[4] = stem; in_channels = [C(f0), 256, 128, 64, 32],
+    // skip_channels = [C(f1), C(f2), C(f3), C(f4), 0], out_channels = dec.  Node x_d_l = DecoderBlock(up(x_d_(l-1) or f[d]),
+    // cat(x_(d+1)_l .. x_l_l, f[l+1])); all nodes x_*_l and f[l+1] share a resolution.  Parameters are REGISTERED in the
+    // constructor's order (x_0_0; x_0_1 x_1_1; x_0_2 x_1_2 x_2_2; ..; x_0_4) but EXECUTED in forward()'s order
+    // (x_0_0 x_1_1 x_2_2 x_3_3; x_0_1 x_1_2 x_2_3; x_0_2 x_1_3; x_0_3; x_0_4): tensors first, units second.
+    const int* dec = kDecoderChannels;
+    const int f_act[5] = {f.feat[5], f.feat[4], f.feat[3], f.feat[2], f.feat[1]};
+    const int f_c[5] = {f.featc[5], f.featc[4], f.featc[3], f.featc[2], f.featc[1]};
+    const int skipc[5] = {f_c[1], f_c[2], f_c[3], f_c[4], 0};
+    const int in_c[5] = {f_c[0], dec[0], dec[1], dec[2], dec[3]};
+    struct Node { int skip_ch, out_ch, out_act; DecoderBlockTensors t; };
+    Node node[5][5] = {};
+    auto reg = [&](int d, int l, int in_ch, int skip_ch, int out_ch) {
+        node[d][l].skip_ch = skip_ch; node[d][l].out_ch = out_ch;
+        node[d][l].t = decoder_block_tensors(B, "decoder.blocks.x_" + std::to_string(d) + "_" + std::to_string(l), in_ch + skip_ch, out_ch);
+    };
+    for (int l = 0; l < 4; ++l)
+        for (int d = 0; d <= l; ++d) {
+            if (d == 0) reg(0, l, in_c[l], skipc[l] * (l + 1), dec[l]);
+            else reg(d, l, skipc[l - 1], skipc[l] * (l + 1 - d), skipc[l]);
+        }
+    reg(0, 4, in_c[4], 0, dec[4]);
+    auto run_node = [&](int d, int l, int x_act, int x_c, std::vector<int> skips) {
+        Node& nd = node[d][l];
+        // on the loader's route the concatenation of the skips is materialised (channel-slice copies, also for a single member): its gradient is split back
+        if (!skips.empty() && x_c % 32 == 0) skips = {B.concat(skips, nd.skip_ch, 2 * B.A[x_act].h, 2 * B.A[x_act].w)};
+        nd.out_act = decoder_block(B, nd.t, x_act, x_c, skips, nd.skip_ch, nd.out_ch);
+    };
+    for (int layer = 0; layer < 4; ++layer)
+        for (int d = 0; d < 4 - layer; ++d) {
+            const int l = d + layer;
+            if (layer == 0) {
+                run_node(d, d, f_act[d], f_c[d], {f_act[d + 1]});
+            } else {
+                std::vector<int> members;
+                for (int idx = d + 1; idx <= l; ++idx) members.push_back(node[idx][l].out_act);
+                members.push_back(f_act[l + 1]);
+                run_node(d, l, node[d][l - 1].out_act, node[d][l - 1].out_ch, members);
+            }
+        }
+    run_node(0, 4, node[0][3].out_act, node[0][3].out_ch, {});
+    return {node[0][4].out_act, dec[4], 3, 1};
+}
+
+HeadInput decoder_linknet(Builder& B, const Features& f) {
+    // smp.Linknet (decoders/linknet/decoder.py of segmentation-models-pytorch 0.2.1, restated): channels = reversed encoder
+    // features (deepest first) + [32]; block i = Conv2dReLU(in, in/4, 1) -> TransposeX2(in/4, in/4) -> Conv2dReLU(in/4, out, 1),
+    // then + skip (the next-shallower encoder feature) for i < 4; head = Conv2d(32, classes, 1).
+    const int chans[6] = {f.featc[5], f.featc[4], f.featc[3], f.featc[2], f.featc[1], 32};
+    const int skips[5] = {f.feat[4], f.feat[3], f.feat[2], f.feat[1], -1};
+    int x = f.feat[5], xh = B.A[x].h, xw = B.A[x].w;
+    for (int i = 0; i < 5; ++i) {
+        const std::string pre = "decoder.blocks." + std::to_string(i) + ".block.";
+        const int cin = chans[i], mid = cin / 4, cout = chans[i + 1];
+        x = B.emit(B.conv_unit(pre + "0.0.weight", "", pre + "0.1", x, cin, mid, 1, 1, xh, xw));
+        Unit ut = Builder::conv(x, mid, mid, 3, 1, xh, xw);
+        ut.kind = U_CONVT; ut.hout = 2 * xh; ut.wout = 2 * xw;
+        ut.w_idx = B.tensor(pre + "1.0.weight", {mid, mid, 4, 4}, 3);   // torch's [in][out][kh][kw], as is
+        B.attach_bias(ut, pre + "1.0.bias");
+        B.attach_bn(ut, pre + "1.1");
+        ut.out = B.act(mid, 2 * xh, 2 * xw, true);
+        x = B.emit(ut);
+        xh *= 2; xw *= 2;
+        x = B.emit(B.conv_unit(pre + "2.0.weight", "", pre + "2.1", x, mid, cout, 1, 1, xh, xw));
+        if (skips[i] >= 0) x = B.op(U_ADD, x, skips[i], cout, 0, 0, xh, xw).out;
+    }
+    return {x, 32, 1, 1};
+}
+
+HeadInput decoder_fpn(Builder& B, const Features& f) {
+    // smp.FPN (decoders/fpn/decoder.py of segmentation-models-pytorch 0.2.1, restated): p5 = Conv1x1(c5); p_k = nearest-x2(p_(k+1)) +
+    // Conv1x1(c_k) for k = 4, 3, 2 (pyramid_channels 256, biased, no norm); seg_blocks[i] on p5, p4, p3, p2 with 3, 2, 1, 0
+    // upsamplings: Conv3x3(256 -> 128, no bias) + GroupNorm(32) + ReLU (+ bilinear x2, align_corners) then (ups - 1) x
+    // [Conv3x3(128 -> 128) + GN + ReLU + bilinear x2]; merge = sum; Dropout2d(0.2); head = Conv1x1(128 -> classes) +
+    // UpsamplingBilinear2d(4).
+    const int pyr = 256, seg = 128;
+    auto lateral = [&](const std::string& name, int src, int cin) {
+        Unit u = B.conv_unit(name + ".weight", name + ".bias", "", src, cin, pyr, 1, 1, B.A[src].h, B.A[src].w);
+        u.relu = 0;
+        return B.emit(u);
+    };
+    int pyramid[4];
+    pyramid[0] = lateral("decoder.p5", f.feat[5], f.featc[5]);
+    for (int k = 0; k < 3; ++k) {   // p4, p3, p2
+        const int lat = lateral("decoder.p" + std::to_string(4 - k) + ".skip_conv", f.feat[4 - k], f.featc[4 - k]);
+        const Act la = B.A[lat];
+        pyramid[k + 1] = B.op(U_UPADD, pyramid[k], lat, pyr, la.h / 2, la.w / 2, la.h, la.w).out;
+    }
+    int merged = -1;
+    for (int i = 0; i < 4; ++i) {
+        const int ups = 3 - i;
+        int x = pyramid[i], x_c = pyr;
+        for (int j = 0; j < std::max(1, ups); ++j) {
+            const std::string pre = "decoder.seg_blocks." + std::to_string(i) + ".block." + std::to_string(j) + ".block.";
+            const Act xa = B.A[x];
+            Unit u = Builder::conv(x, x_c, seg, 3, 1, xa.h, xa.w);
+            B.attach_weight(u, pre + "0.weight");
+            B.attach_gn(u, pre + "1", 32);
+            u.out = B.act(seg, xa.h, xa.w, true);
+            x = B.emit(u); x_c = seg;
+            if (ups > 0) x = B.op(U_BILINEAR, x, -1, seg, xa.h, xa.w, 2 * xa.h, 2 * xa.w).out;
+        }
+        merged = merged < 0 ? x : B.op(U_ADD, merged, x, seg, 0, 0, B.A[merged].h, B.A[merged].w).out;
+    }
+    const int dropped = B.op(U_DROPOUT, merged, -1, seg, 0, 0, B.A[merged].h, B.A[merged].w).out;
+    return {dropped, seg, 1, 4};
+}
+
+// smp's ASPP(C5, 256, rates (12, 24, 36)) + Dropout(0.5) on the deepest feature, tensors under `pre`: convs = [1x1 conv + BN + ReLU,
+// 3 x branch(prefix of convs.r, rate), ASPPPooling = Sequential(AdaptiveAvgPool2d(1), Conv2d, BatchNorm2d, ReLU) + F.interpolate(size,
+// bilinear, align_corners=False) back to the map], concat, project = 1x1 conv (1280 -> 256) + BN + ReLU + Dropout(0.5).
+// conv_bn(wname, bnname, src, cin, cout, h, w, k) and branch(prefix, rate) are the caller's: dense dilated 3x3 (DeepLabV3) / separable (DeepLabV3+)
+template <class ConvBn, class Branch>
+int aspp(Builder& B, const std::string& pre, const Features& f, ConvBn conv_bn, Branch branch) {
+    const int c5 = f.feat[5], c5c = f.featc[5], ah = B.A[c5].h, aw = B.A[c5].w;
+    std::vector<int> branches;
+    branches.push_back(conv_bn(pre + ".convs.0.0.weight", pre + ".convs.0.1", c5, c5c, 256, ah, aw, 1));
+    const int rates[3] = {12, 24, 36};
+    for (int r = 0; r < 3; ++r) branches.push_back(branch(pre + ".convs." + std::to_string(r + 1), rates[r]));
+    const int pooled = conv_bn(pre + ".convs.4.1.weight", pre + ".convs.4.2", B.gap(c5, c5c, ah, aw), c5c, 256, 1, 1, 1);
+    branches.push_back(B.op(U_BCAST, pooled, -1, 256, 1, 1, ah, aw).out);
+    const int cat = B.concat(branches, 5 * 256, ah, aw);
+    const int proj = conv_bn(pre + ".project.0.weight", pre + ".project.1", cat, 5 * 256, 256, ah, aw, 1);
+    return B.op(U_DROPOUT_E, proj, -1, 256, 0, 0, ah, aw).out;
+}
+
+HeadInput decoder_deeplabv3(Builder& B, const Features& f) {
+    // smp.DeepLabV3 (decoders/deeplabv3/decoder.py, restated; encoder_output_stride 8): DeepLabV3Decoder = Sequential(ASPP(C5, 256,
+    // rates (12, 24, 36)), Conv2d(256, 256, 3, padding=1, bias=False), BatchNorm2d, ReLU); ASPP as in DeepLabV3+ but with DENSE
+    // dilated 3x3 branches (ASPPConv); head = Conv2d(256, classes, 1) + UpsamplingBilinear2d(8).
+    const int c5 = f.feat[5], c5c = f.featc[5], ah = B.A[c5].h, aw = B.A[c5].w;
+    auto conv_bn = [&](const std::string& wname, const std::string& bnname, int src, int cin, int cout, int hh, int ww, int k, int rate = 0) {
+        Unit u = B.conv_unit(wname, "", bnname, src, cin, cout, k, 1, hh, ww);
+        u.colr = rate;
+        return B.emit(u);
+    };
+    const int dropped = aspp(B, "decoder.0", f, conv_bn,
+                             [&](const std::string& pre, int rate) { return conv_bn(pre + ".0.weight", pre + ".1", c5, c5c, 256, ah, aw, 3, rate); });
+    return {conv_bn("decoder.1.weight", "decoder.2", dropped, 256, 256, ah, aw, 3), 256, 1, 8};
+}
+
+HeadInput decoder_deeplabv3plus(Builder& B, const Features& f) {
+    // smp.DeepLabV3Plus (decoders/deeplabv3/decoder.py of segmentation-models-pytorch 0.2.1, restated; encoder_output_stride 16:
+    // layer4 dilated above).  aspp = Sequential(ASPP(C5, 256, rates (12, 24, 36), separable), SeparableConv2d(256, 256, 3), BN,
+    // ReLU); ASPP: convs = [1x1 conv + BN + ReLU, 3 x (SeparableConv2d(C5, 256, 3, dilation r) + BN + ReLU), AdaptiveAvgPool2d(1)
+    // + 1x1 conv + BN + ReLU + bilinear back to the map], concat, project = 1x1 conv (1280 -> 256) + BN + ReLU + Dropout(0.5);
+    // up = UpsamplingBilinear2d(4); block1 = 1x1 conv (C2 -> 48) + BN + ReLU on the stride-4 feature; concat; block2 =
+    // SeparableConv2d(304, 256, 3) + BN + ReLU; head = Conv2d(256, classes, 1) + UpsamplingBilinear2d(4).
+    // SeparableConv2d = depthwise 3x3 (dilation = padding) then pointwise 1x1, no norm in between, both without bias.
+    const int c5 = f.feat[5], c5c = f.featc[5], ah = B.A[c5].h, aw = B.A[c5].w;
+    auto conv_bn = [&](const std::string& wname, const std::string& bnname, int src, int cin, int cout, int hh, int ww, int k) {
+        return B.emit(B.conv_unit(wname, "", bnname, src, cin, cout, k, 1, hh, ww));
+    };
+    auto separable_bn = [&](const std::string& pre_conv, const std::string& bnname, int src, int cin, int cout, int hh, int ww, int dil) {
+        Unit d; d.kind = U_DWCONV; d.src0 = src; d.cin0 = cin; d.cout = cin; d.k = 3; d.dil = dil; d.pad = dil; d.relu = 0;
+        d.hin = hh; d.win = ww; d.hout = hh; d.wout = ww;
+        d.w_idx = B.weight(pre_conv + ".0.weight", {cin, 1, 3, 3});
+        d.out = B.act(cin, hh, ww, false);
+        // the pointwise convolution's weight follows the depthwise one in the state dict, its BatchNorm after both
+        const Unit u = B.conv_unit(pre_conv + ".1.weight", "", bnname, d.out, cin, cout, 1, 1, hh, ww);
+        B.emit(d);
+        return B.emit(u);
+    };
+    const int dropped = aspp(B, "decoder.aspp.0", f, conv_bn,
+                             [&](const std::string& pre, int rate) { return separable_bn(pre + ".0", pre + ".1", c5, c5c, 256, ah, aw, rate); });
+    const int deep = separable_bn("decoder.aspp.1", "decoder.aspp.2", dropped, 256, 256, ah, aw, 1);
+    Unit& up = B.op(U_BILINEAR, deep, -1, 256, ah, aw, 4 * ah, 4 * aw);
+    up.factor = 4;
+    const int up_act = up.out;
+    const Act hr = B.A[f.feat[2]];
+    const int high = conv_bn("decoder.block1.0.weight", "decoder.block1.1", f.feat[2], f.featc[2], 48, hr.h, hr.w, 1);
+    const int cat2 = B.concat({up_act, high}, 256 + 48, hr.h, hr.w);
+    return {separable_bn("decoder.block2.0", "decoder.block2.1", cat2, 256 + 48, 256, hr.h, hr.w, 1), 256, 1, 4};
+}
+
+HeadInput decoder_manet(Builder& B, const Features& f) {
+    // smp.MAnet (decoders/manet/decoder.py of segmentation-models-pytorch 0.2.1, restated): center = PAB(C5, pab_channels 64):
+    // top / center 1x1 convs (C5 -> 64), bottom 3x3 conv (C5 -> C5), all biased, attention (vs_pab_attention_*), out_conv 3x3
+    // (biased).  blocks[i] = MFAB(in, skip, out, reduction 16) for the four levels with a skip: hl_conv = Conv3x3(in, in) + BN +
+    // ReLU, Conv1x1(in, skip) + BN + ReLU; nearest x2; SE_hl on it, SE_ll on the skip (AdaptiveAvgPool2d(1), Conv1x1(skip,
+    // skip / 16), ReLU, Conv1x1(-> skip), Sigmoid); x * (SE_hl + SE_ll); cat skip; conv1, conv2 (3x3 + BN + ReLU);
+    // blocks[4] = U-Net's DecoderBlock(32, 0, 16).  The gate commutes with the nearest upsampling, so it is applied at the
+    // low resolution and conv1 reads up(x * gate) ++ skip through its loader, as the U-Net decoder does.
+    const int C5 = f.featc[5];
+    const Act fa = B.A[f.feat[5]];
+    auto plain = [&](const std::string& name, int src, int cin, int cout, int k) {
+        Unit u = B.conv_unit(name + ".weight", name + ".bias", "", src, cin, cout, k, 1, fa.h, fa.w);
+        u.relu = 0;
+        return B.emit(u);
+    };
+    const int top = plain("decoder.center.top_conv", f.feat[5], C5, 64, 1);
+    const int cen = plain("decoder.center.center_conv", f.feat[5], C5, 64, 1);
+    const int bot = plain("decoder.center.bottom_conv", f.feat[5], C5, C5, 3);
+    Unit& pab = B.op(U_PAB, f.feat[5], -1, C5, 0, 0, fa.h, fa.w);
+    pab.members = {top, cen, bot}; pab.cin0 = 64;
+    int x = plain("decoder.center.out_conv", pab.out, C5, C5, 3), x_c = C5, xh = fa.h, xw = fa.w;
+    const int* dec = kDecoderChannels;
     for (int i = 0; i < 5; ++i) {
         const std::string pre = "decoder.blocks." + std::to_string(i);
-        const int oh = ch * 2, ow = cw * 2;
-        Unit u1; u1.kind = U_CONV; u1.src0 = xin; u1.up0 = 1; u1.cin0 = xc; u1.cin1 = skipc[i];
-        u1.src1 = skipc[i] ? feat[4 - i] : -1; u1.cout = dec[i];
-        u1.hin = oh; u1.win = ow; u1.hout = oh; u1.wout = ow;
-        u1.w_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv1.0.weight", {dec[i], xc + skipc[i], 3, 3}, 0);
-        u1.bn_idx = add_bn(L, pre + ".conv1.1", dec[i]);
-        u1.out = new_act(dec[i], oh, ow, true);
-        Unit u2; u2.kind = U_CONV; u2.src0 = u1.out; u2.cin0 = dec[i]; u2.cout = dec[i];
-        u2.hin = oh; u2.win = ow; u2.hout = oh; u2.wout = ow;
-        u2.w_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv2.0.weight", {dec[i], dec[i], 3, 3}, 0);
-        u2.bn_idx = add_bn(L, pre + ".conv2.1", dec[i]);
-        u2.out = new_act(dec[i], oh, ow, true);
-        U.push_back(u1); U.push_back(u2);
-        xin = u2.out; xc = dec[i]; ch = oh; cw = ow;
+        const int S = i < 4 ? f.featc[4 - i] : 0, skip = i < 4 ? f.feat[4 - i] : -1;
+        if (S > 0) {
+            const int h0 = B.emit(B.conv_unit(pre + ".hl_conv.0.0.weight", "", pre + ".hl_conv.0.1", x, x_c, x_c, 3, 1, xh, xw));
+            const int h1 = B.emit(B.conv_unit(pre + ".hl_conv.1.0.weight", "", pre + ".hl_conv.1.1", h0, x_c, S, 1, 1, xh, xw));
+            const int R = std::max(1, S / 16);
+            const int w_ll = B.se_tensors(pre + ".SE_ll.1", pre + ".SE_ll.3", S, R);      // registration order: ll, then hl
+            const int w_hl = B.se_tensors(pre + ".SE_hl.1", pre + ".SE_hl.3", S, R);
+            const int a_hl = B.se(B.gap(h1, S, xh, xw), S, R, w_hl, 0);
+            const int a_ll = B.se(B.gap(skip, S, 2 * xh, 2 * xw), S, R, w_ll, 0);
+            const int gate = B.op(U_ADD, a_hl, a_ll, S, 0, 0, 1, 1).out;
+            x = B.op(U_CGATE, h1, gate, S, 0, 0, xh, xw).out; x_c = S;
+        }
+        const DecoderBlockTensors t = decoder_block_tensors(B, pre, x_c + S, dec[i]);
+        x = decoder_block(B, t, x, x_c, S > 0 ? std::vector<int>{skip} : std::vector<int>{}, S, dec[i], true);
+        x_c = dec[i]; xh *= 2; xw *= 2;
     }
-    } else {
-        // smp.UnetPlusPlusDecoder (decoders/unetplusplus/decoder.py of segmentation-models-pytorch 0.2.1, restated):
-        // features reversed, deepest first: f[0] = layer4 .. f[4] = stem; in_channels = [C(f0), 256, 128, 64, 32],
-        // skip_channels = [C(f1), C(f2), C(f3), C(f4), 0], out_channels = dec.  Node x_d_l = DecoderBlock(up(x_d_(l-1) or f[d]),
-        // cat(x_(d+1)_l .. x_l_l, f[l+1])); all nodes x_*_l and f[l+1] share a resolution.  Parameters are REGISTERED in the
-        // constructor's order (x_0_0; x_0_1 x_1_1; x_0_2 x_1_2 x_2_2; ..; x_0_4) but EXECUTED in forward()'s order
-        // (x_0_0 x_1_1 x_2_2 x_3_3; x_0_1 x_1_2 x_2_3; x_0_2 x_1_3; x_0_3; x_0_4): tensors first, units second.
-        const int f_act[5] = {feat[5], feat[4], feat[3], feat[2], feat[1]};
-        const int f_c[5] = {featc[5], featc[4], featc[3], featc[2], featc[1]};
-        const int in_c[5] = {f_c[0], dec[0], dec[1], dec[2], dec[3]};
-        struct Node { int in_ch, skip_ch, out_ch, w1, bn1, w2, bn2, out_act; };
-        Node node[5][5] = {};
-        auto reg = [&](int d, int l, int in_ch, int skip_ch, int out_ch) {
-            const std::string pre = "decoder.blocks.x_" + std::to_string(d) + "_" + std::to_string(l);
-            Node& nd = node[d][l];
-            nd.in_ch = in_ch; nd.skip_ch = skip_ch; nd.out_ch = out_ch;
-            nd.w1 = (int)L.tensors.size(); add_tensor(L, pre + ".conv1.0.weight", {out_ch, in_ch + skip_ch, 3, 3}, 0);
-            nd.bn1 = add_bn(L, pre + ".conv1.1", out_ch);
-            nd.w2 = (int)L.tensors.size(); add_tensor(L, pre + ".conv2.0.weight", {out_ch, out_ch, 3, 3}, 0);
-            nd.bn2 = add_bn(L, pre + ".conv2.1", out_ch);
-        };
-        for (int l = 0; l < 4; ++l)
-            for (int d = 0; d <= l; ++d) {
-                if (d == 0) reg(0, l, in_c[l], skipc[l] * (l + 1), dec[l]);
-                else reg(d, l, skipc[l - 1], skipc[l] * (l + 1 - d), skipc[l]);
-            }
-        reg(0, 4, in_c[4], 0, dec[4]);
-        auto run_node = [&](int d, int l, int x_act, int x_c, const std::vector<int>& skip_members) {
-            Node& nd = node[d][l];
-            const Act xa = A[x_act];
-            const int oh = xa.h * 2, ow = xa.w * 2;
-            if (!skip_members.empty() && x_c % 32 != 0) {   // (EfficientNet features of 136 / 56 / 48 channels as the upsampled input)
-                const int cat = materialised_cat(x_act, x_c, skip_members, nd.skip_ch);
-                Unit u1; u1.kind = U_CONV; u1.src0 = cat; u1.cin0 = x_c + nd.skip_ch; u1.cout = nd.out_ch; u1.hin = oh; u1.win = ow; u1.hout = oh; u1.wout = ow;
-                u1.w_idx = nd.w1; u1.bn_idx = nd.bn1; u1.out = new_act(nd.out_ch, oh, ow, true);
-                Unit u2; u2.kind = U_CONV; u2.src0 = u1.out; u2.cin0 = nd.out_ch; u2.cout = nd.out_ch;
-                u2.hin = oh; u2.win = ow; u2.hout = oh; u2.wout = ow; u2.w_idx = nd.w2; u2.bn_idx = nd.bn2;
-                u2.out = new_act(nd.out_ch, oh, ow, true);
-                U.push_back(u1); U.push_back(u2);
-                nd.out_act = u2.out;
-                return;
-            }
-            int skip_act = -1;
-            if (!skip_members.empty()) {   // the concatenation is materialised (channel-slice copies): its gradient is split back
-                Unit cu; cu.kind = U_CONCAT; cu.members = skip_members; cu.cout = nd.skip_ch; cu.hout = oh; cu.wout = ow; cu.relu = 0;
-                cu.out = new_act(nd.skip_ch, oh, ow, false);
-                U.push_back(cu);
-                skip_act = cu.out;
-            }
-            Unit u1; u1.kind = U_CONV; u1.src0 = x_act; u1.up0 = 1; u1.cin0 = x_c; u1.cin1 = nd.skip_ch; u1.src1 = skip_act;
-            u1.cout = nd.out_ch; u1.hin = oh; u1.win = ow; u1.hout = oh; u1.wout = ow; u1.w_idx = nd.w1; u1.bn_idx = nd.bn1;
-            u1.out = new_act(nd.out_ch, oh, ow, true);
-            Unit u2; u2.kind = U_CONV; u2.src0 = u1.out; u2.cin0 = nd.out_ch; u2.cout = nd.out_ch;
-            u2.hin = oh; u2.win = ow; u2.hout = oh; u2.wout = ow; u2.w_idx = nd.w2; u2.bn_idx = nd.bn2;
-            u2.out = new_act(nd.out_ch, oh, ow, true);
-            U.push_back(u1); U.push_back(u2);
-            nd.out_act = u2.out;
-        };
-        for (int layer = 0; layer < 4; ++layer)
-            for (int d = 0; d < 4 - layer; ++d) {
-                const int l = d + layer;
-                if (layer == 0) {
-                    run_node(d, d, f_act[d], f_c[d], {f_act[d + 1]});
-                } else {
-                    std::vector<int> members;
-                    for (int idx = d + 1; idx <= l; ++idx) members.push_back(node[idx][l].out_act);
-                    members.push_back(f_act[l + 1]);
-                    run_node(d, l, node[d][l - 1].out_act, node[d][l - 1].out_ch, members);
-                }
-            }
-        run_node(0, 4, node[0][3].out_act, node[0][3].out_ch, {});
-        xin = node[0][4].out_act; xc = dec[4];
+    return {x, 16, 3, 1};
+}
+
+HeadInput decoder_pan(Builder& B, const Features& f) {
+    // smp.PAN (decoders/pan/decoder.py of segmentation-models-pytorch 0.2.1, restated; decoder_channels 32, encoder_dilation).
+    // ConvBnRelu = biased Conv2d + BatchNorm2d (+ ReLU).  FPABlock(C5, 32): branch1 = AdaptiveAvgPool2d(1) + ConvBnRelu 1x1
+    // (broadcast back), mid = ConvBnRelu 1x1, the single-channel pyramid (down1 .. conv1, vs_fpa_pyramid_*), out = plane * mid +
+    // branch1.  GAUBlock(Ck, 32)(x, y): conv1 = AdaptiveAvgPool2d(1) + ConvBnRelu 1x1 without ReLU + Sigmoid on y, conv2 =
+    // ConvBnRelu 3x3 on x; out = bilinear(y -> x's size) + conv2(x) * conv1(y).  gau3 / gau2 / gau1 on the stride-16 / 8 / 4
+    // features; head = Conv2d(32, classes, 3, padding 1) + UpsamplingBilinear2d(4).
+    const int C5 = f.featc[5];
+    const Act fa = B.A[f.feat[5]];
+    // described, not emitted: the convolutions' tensors are registered and their outputs allocated in the constructor's order, ahead of
+    // the pools that feed them and run first
+    auto cbr_bias = [&](const std::string& pre, int src, int cin, int cout, int k, int hh, int ww, int relu) {
+        Unit u = B.conv_unit(pre + ".conv.weight", pre + ".conv.bias", pre + ".bn", src, cin, cout, k, 1, hh, ww);
+        u.relu = relu;
+        return u;
+    };
+    // ---- FPA ----
+    Unit b1 = cbr_bias("decoder.fpa.branch1.1", -1, C5, 32, 1, 1, 1, 1);
+    Unit mid = cbr_bias("decoder.fpa.mid.0", f.feat[5], C5, 32, 1, fa.h, fa.w, 1);
+    Unit fpa; fpa.kind = U_FPA; fpa.src0 = f.feat[5]; fpa.cin0 = C5; fpa.cout = 32; fpa.hin = fa.h; fpa.win = fa.w; fpa.hout = fa.h; fpa.wout = fa.w; fpa.relu = 0;
+    {
+        const char* names[6] = {"decoder.fpa.down1.1", "decoder.fpa.down2.1", "decoder.fpa.down3.1", "decoder.fpa.down3.2", "decoder.fpa.conv2", "decoder.fpa.conv1"};
+        const int ks[6] = {7, 5, 3, 3, 5, 7};
+        for (int i = 0; i < 6; ++i) {
+            fpa.tens.push_back(B.weight(std::string(names[i]) + ".conv.weight", {1, i == 0 ? C5 : 1, ks[i], ks[i]}));
+            fpa.tens.push_back(B.bias(std::string(names[i]) + ".conv.bias", 1));
+            const int g = B.bn(std::string(names[i]) + ".bn", 1);
+            fpa.tens.push_back(g); fpa.tens.push_back(g + 1);
+        }
+        fpa.w_idx = fpa.tens[0];
     }
-    int head_k = 3, head_h = H, head_w = W;
-    if (net->topology == 7) {
-        // smp.PAN (decoders/pan/decoder.py of segmentation-models-pytorch 0.2.1, restated; decoder_channels 32, encoder_dilation).
-        // ConvBnRelu = biased Conv2d + BatchNorm2d (+ ReLU).  FPABlock(C5, 32): branch1 = AdaptiveAvgPool2d(1) + ConvBnRelu 1x1
-        // (broadcast back), mid = ConvBnRelu 1x1, the single-channel pyramid (down1 .. conv1, vs_fpa_pyramid_*), out = plane * mid +
-        // branch1.  GAUBlock(Ck, 32)(x, y): conv1 = AdaptiveAvgPool2d(1) + ConvBnRelu 1x1 without ReLU + Sigmoid on y, conv2 =
-        // ConvBnRelu 3x3 on x; out = bilinear(y -> x's size) + conv2(x) * conv1(y).  gau3 / gau2 / gau1 on the stride-16 / 8 / 4
-        // features; head = Conv2d(32, classes, 3, padding 1) + UpsamplingBilinear2d(4).
-        const int C5 = featc[5];
-        const Act fa = A[feat[5]];
-        auto cbr_bias = [&](const std::string& pre, int src, int cin, int cout, int k, int hh, int ww, int relu) {
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2; u.relu = relu;
-            u.hin = hh; u.win = ww; u.hout = hh; u.wout = ww;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv.weight", {cout, cin, k, k}, 0);
-            u.bias_idx = (int)L.tensors.size(); add_tensor(L, pre + ".conv.bias", {cout}, 3);
-            u.bn_idx = add_bn(L, pre + ".bn", cout);
-            u.out = new_act(cout, hh, ww, true);
-            return u;
-        };
-        auto gap = [&](int src, int cch, int hh, int ww) {
-            Unit gp; gp.kind = U_GAP; gp.src0 = src; gp.cout = cch; gp.hin = hh; gp.win = ww; gp.hout = 1; gp.wout = 1; gp.relu = 0;
-            gp.out = new_act(cch, 1, 1, false);
-            U.push_back(gp);
-            return gp.out;
-        };
-        // ---- FPA ----
-        Unit b1 = cbr_bias("decoder.fpa.branch1.1", -1, C5, 32, 1, 1, 1, 1);
-        Unit mid = cbr_bias("decoder.fpa.mid.0", feat[5], C5, 32, 1, fa.h, fa.w, 1);
-        Unit fpa; fpa.kind = U_FPA; fpa.src0 = feat[5]; fpa.cin0 = C5; fpa.cout = 32; fpa.hin = fa.h; fpa.win = fa.w; fpa.hout = fa.h; fpa.wout = fa.w; fpa.relu = 0;
-        {
-            const char* names[6] = {"decoder.fpa.down1.1", "decoder.fpa.down2.1", "decoder.fpa.down3.1", "decoder.fpa.down3.2", "decoder.fpa.conv2", "decoder.fpa.conv1"};
-            const int ks[6] = {7, 5, 3, 3, 5, 7};
-            for (int i = 0; i < 6; ++i) {
-                fpa.tens.push_back((int)L.tensors.size()); add_tensor(L, std::string(names[i]) + ".conv.weight", {1, i == 0 ? C5 : 1, ks[i], ks[i]}, 0);
-                fpa.tens.push_back((int)L.tensors.size()); add_tensor(L, std::string(names[i]) + ".conv.bias", {1}, 3);
-                const int g = add_bn(L, std::string(names[i]) + ".bn", 1);
-                fpa.tens.push_back(g); fpa.tens.push_back(g + 1);
-            }
-            fpa.w_idx = fpa.tens[0];
-        }
-        b1.src0 = gap(feat[5], C5, fa.h, fa.w);
-        U.push_back(b1); U.push_back(mid);
-        fpa.src1 = mid.out; fpa.res = b1.out;
-        fpa.out = new_act(32, fa.h, fa.w, false);
-        U.push_back(fpa);
-        // ---- GAU x 3 ----
-        int y_act = fpa.out;
-        const int gx[3] = {feat[4], feat[3], feat[2]};
-        const int gc[3] = {featc[4], featc[3], featc[2]};
-        for (int i = 0; i < 3; ++i) {
-            const std::string pre = "decoder.gau" + std::to_string(3 - i);
-            const Act xa = A[gx[i]], ya = A[y_act];
-            Unit c1 = cbr_bias(pre + ".conv1.1", -1, 32, 32, 1, 1, 1, 0);      // registered first, as in smp's constructor
-            Unit c2 = cbr_bias(pre + ".conv2", gx[i], gc[i], 32, 3, xa.h, xa.w, 1);
-            c1.src0 = gap(y_act, 32, ya.h, ya.w);
-            U.push_back(c1);
-            Unit sg; sg.kind = U_SIGMOID; sg.src0 = c1.out; sg.cout = 32; sg.hout = 1; sg.wout = 1; sg.relu = 0;
-            sg.out = new_act(32, 1, 1, false);
-            U.push_back(sg);
-            U.push_back(c2);
-            Unit cg; cg.kind = U_CGATE; cg.src0 = c2.out; cg.src1 = sg.out; cg.cout = 32; cg.hout = xa.h; cg.wout = xa.w; cg.relu = 0;
-            cg.out = new_act(32, xa.h, xa.w, false);
-            U.push_back(cg);
-            Unit up; up.kind = U_BILINEAR; up.src0 = y_act; up.cout = 32; up.factor = xa.h / ya.h; up.hin = ya.h; up.win = ya.w; up.hout = xa.h; up.wout = xa.w; up.relu = 0;
-            up.out = new_act(32, xa.h, xa.w, false);
-            U.push_back(up);
-            Unit ad; ad.kind = U_ADD; ad.src0 = up.out; ad.src1 = cg.out; ad.cout = 32; ad.hout = xa.h; ad.wout = xa.w; ad.relu = 0;
-            ad.out = new_act(32, xa.h, xa.w, false);
-            U.push_back(ad);
-            y_act = ad.out;
-        }
-        xin = y_act; xc = 32; head_k = 3; head_h = A[y_act].h; head_w = A[y_act].w;
-        net->head_up = 4;
+    b1.src0 = B.gap(f.feat[5], C5, fa.h, fa.w);
+    fpa.res = B.emit(b1);
+    fpa.src1 = B.emit(mid);
+    fpa.out = B.act(32, fa.h, fa.w, false);
+    // ---- GAU x 3 ----
+    int y = B.emit(fpa);
+    for (int i = 0; i < 3; ++i) {
+        const std::string pre = "decoder.gau" + std::to_string(3 - i);
+        const int gx = f.feat[4 - i];
+        const Act xa = B.A[gx], ya = B.A[y];
+        Unit c1 = cbr_bias(pre + ".conv1.1", -1, 32, 32, 1, 1, 1, 0);      // registered first, as in smp's constructor
+        Unit c2 = cbr_bias(pre + ".conv2", gx, f.featc[4 - i], 32, 3, xa.h, xa.w, 1);
+        c1.src0 = B.gap(y, 32, ya.h, ya.w);
+        const int gate = B.op(U_SIGMOID, B.emit(c1), -1, 32, 0, 0, 1, 1).out;
+        const int gated = B.op(U_CGATE, B.emit(c2), gate, 32, 0, 0, xa.h, xa.w).out;
+        Unit& up = B.op(U_BILINEAR, y, -1, 32, ya.h, ya.w, xa.h, xa.w);
+        up.factor = xa.h / ya.h;
+        y = B.op(U_ADD, up.out, gated, 32, 0, 0, xa.h, xa.w).out;
     }
-    if (net->topology == 6) {
-        // smp.MAnet (decoders/manet/decoder.py of segmentation-models-pytorch 0.2.1, restated): center = PAB(C5, pab_channels 64):
-        // top / center 1x1 convs (C5 -> 64), bottom 3x3 conv (C5 -> C5), all biased, attention (vs_pab_attention_*), out_conv 3x3
-        // (biased).  blocks[i] = MFAB(in, skip, out, reduction 16) for the four levels with a skip: hl_conv = Conv3x3(in, in) + BN +
-        // ReLU, Conv1x1(in, skip) + BN + ReLU; nearest x2; SE_hl on it, SE_ll on the skip (AdaptiveAvgPool2d(1), Conv1x1(skip,
-        // skip / 16), ReLU, Conv1x1(-> skip), Sigmoid); x * (SE_hl + SE_ll); cat skip; conv1, conv2 (3x3 + BN + ReLU);
-        // blocks[4] = U-Net's DecoderBlock(32, 0, 16).  The gate commutes with the nearest upsampling, so it is applied at the
-        // low resolution and conv1 reads up(x * gate) ++ skip through its loader, as the U-Net decoder does.
-        const int C5 = featc[5];
-        const Act fa = A[feat[5]];
-        auto plain = [&](const std::string& name, int src, int cin, int cout, int k) {
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2; u.relu = 0;
-            u.hin = fa.h; u.win = fa.w; u.hout = fa.h; u.wout = fa.w;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, name + ".weight", {cout, cin, k, k}, 0);
-            u.bias_idx = (int)L.tensors.size(); add_tensor(L, name + ".bias", {cout}, 3);
-            u.out = new_act(cout, fa.h, fa.w, false);
-            U.push_back(u);
-            return u.out;
-        };
-        const int top = plain("decoder.center.top_conv", feat[5], C5, 64, 1);
-        const int cen = plain("decoder.center.center_conv", feat[5], C5, 64, 1);
-        const int bot = plain("decoder.center.bottom_conv", feat[5], C5, C5, 3);
-        Unit pab; pab.kind = U_PAB; pab.src0 = feat[5]; pab.members = {top, cen, bot}; pab.cout = C5; pab.cin0 = 64; pab.hout = fa.h; pab.wout = fa.w; pab.relu = 0;
-        pab.out = new_act(C5, fa.h, fa.w, false);
-        U.push_back(pab);
-        int x_act = plain("decoder.center.out_conv", pab.out, C5, C5, 3), x_c = C5, xh = fa.h, xw = fa.w;
-        const int decm[5] = {256, 128, 64, 32, 16};
-        const int skipa[5] = {feat[4], feat[3], feat[2], feat[1], -1};
-        const int skipcm[5] = {featc[4], featc[3], featc[2], featc[1], 0};
-        auto cbr = [&](const std::string& wname, const std::string& bnname, int src, int cin, int cout, int k, int hh, int ww) {
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2;
-            u.hin = hh; u.win = ww; u.hout = hh; u.wout = ww;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, wname, {cout, cin, k, k}, 0);
-            u.bn_idx = add_bn(L, bnname, cout);
-            u.out = new_act(cout, hh, ww, true);
-            return u;
-        };
-        for (int i = 0; i < 5; ++i) {
-            const std::string pre = "decoder.blocks." + std::to_string(i) + ".";
-            const int S = skipcm[i], oc = decm[i];
-            int up_src = x_act, up_c = x_c;
-            if (S > 0) {
-                Unit h0 = cbr(pre + "hl_conv.0.0.weight", pre + "hl_conv.0.1", x_act, x_c, x_c, 3, xh, xw);
-                U.push_back(h0);
-                Unit h1 = cbr(pre + "hl_conv.1.0.weight", pre + "hl_conv.1.1", h0.out, x_c, S, 1, xh, xw);
-                U.push_back(h1);
-                const int R = std::max(1, S / 16);
-                auto se_tensors = [&](const std::string& nm) {
-                    const int w = (int)L.tensors.size();
-                    add_tensor(L, pre + nm + ".1.weight", {R, S, 1, 1}, 0); add_tensor(L, pre + nm + ".1.bias", {R}, 3);
-                    add_tensor(L, pre + nm + ".3.weight", {S, R, 1, 1}, 0); add_tensor(L, pre + nm + ".3.bias", {S}, 3);
-                    return w;
-                };
-                const int w_ll = se_tensors("SE_ll"), w_hl = se_tensors("SE_hl");      // registration order: ll, then hl
-                auto gate = [&](int src, int hh, int ww, int widx) {
-                    Unit gp; gp.kind = U_GAP; gp.src0 = src; gp.cout = S; gp.hin = hh; gp.win = ww; gp.hout = 1; gp.wout = 1; gp.relu = 0;
-                    gp.out = new_act(S, 1, 1, false);
-                    U.push_back(gp);
-                    Unit se; se.kind = U_SE; se.src0 = gp.out; se.cout = S; se.cin0 = S; se.cin1 = R; se.w_idx = widx; se.hout = 1; se.wout = 1; se.relu = 0;
-                    se.out = new_act(S, 1, 1, false);
-                    U.push_back(se);
-                    return se.out;
-                };
-                const int a_hl = gate(h1.out, xh, xw, w_hl);
-                const int a_ll = gate(skipa[i], 2 * xh, 2 * xw, w_ll);
-                Unit ad; ad.kind = U_ADD; ad.src0 = a_hl; ad.src1 = a_ll; ad.cout = S; ad.hout = 1; ad.wout = 1; ad.relu = 0;
-                ad.out = new_act(S, 1, 1, false);
-                U.push_back(ad);
-                Unit cg; cg.kind = U_CGATE; cg.src0 = h1.out; cg.src1 = ad.out; cg.cout = S; cg.hout = xh; cg.wout = xw; cg.relu = 0;
-                cg.out = new_act(S, xh, xw, false);
-                U.push_back(cg);
-                up_src = cg.out; up_c = S;
-            }
-            xh *= 2; xw *= 2;
-            Unit c1 = cbr(pre + "conv1.0.weight", pre + "conv1.1", up_src, up_c + S, oc, 3, xh, xw);
-            if (S > 0 && up_c % 32 != 0) {     // (EfficientNet skips of 56 / 48 channels: the concatenation is materialised)
-                c1.src0 = materialised_cat(up_src, up_c, {skipa[i]}, S);
-            } else {
-                c1.up0 = 1; c1.cin0 = up_c; c1.cin1 = S; c1.src1 = S > 0 ? skipa[i] : -1;
-            }
-            U.push_back(c1);
-            Unit c2 = cbr(pre + "conv2.0.weight", pre + "conv2.1", c1.out, oc, oc, 3, xh, xw);
-            U.push_back(c2);
-            x_act = c2.out; x_c = oc;
-        }
-        xin = x_act; xc = 16;
+    return {y, 32, 3, 4};
+}
+
+int build(vs_unet* net) {
+    Builder B(net);
+    const Features f = (net->encoder == 103 || net->encoder == 104) ? encoder_efficientnet(B)
+                       : (net->encoder == 150 || net->encoder == 201) ? encoder_resnest(B) : encoder_resnet(B);
+    HeadInput x{};
+    switch (net->topology) {
+        case 0: x = decoder_unet(B, f); break;
+        case 1: x = decoder_unetplusplus(B, f); break;
+        case 2: x = decoder_linknet(B, f); break;
+        case 3: x = decoder_fpn(B, f); break;
+        case 4: x = decoder_deeplabv3plus(B, f); break;
+        case 5: x = decoder_deeplabv3(B, f); break;
+        case 6: x = decoder_manet(B, f); break;
+        default: x = decoder_pan(B, f); break;
     }
-    if (net->topology == 5) {
-        // smp.DeepLabV3 (decoders/deeplabv3/decoder.py, restated; encoder_output_stride 8): DeepLabV3Decoder = Sequential(ASPP(C5, 256,
-        // rates (12, 24, 36)), Conv2d(256, 256, 3, padding=1, bias=False), BatchNorm2d, ReLU); ASPP as in DeepLabV3+ but with DENSE
-        // dilated 3x3 branches (ASPPConv); head = Conv2d(256, classes, 1) + UpsamplingBilinear2d(8).
-        const int c5 = feat[5], c5c = featc[5], ah = A[feat[5]].h, aw = A[feat[5]].w;
-        auto conv_bn = [&](const std::string& wname, const std::string& bnname, int src, int cin, int cout, int hh, int ww, int k, int rate) {
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = k; u.pad = k / 2; u.colr = rate;
-            u.hin = hh; u.win = ww; u.hout = hh; u.wout = ww;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, wname, {cout, cin, k, k}, 0);
-            u.bn_idx = add_bn(L, bnname, cout);
-            u.out = new_act(cout, hh, ww, true);
-            U.push_back(u);
-            return u.out;
-        };
-        std::vector<int> branches;
-        branches.push_back(conv_bn("decoder.0.convs.0.0.weight", "decoder.0.convs.0.1", c5, c5c, 256, ah, aw, 1, 0));
-        const int rates[3] = {12, 24, 36};
-        for (int r = 0; r < 3; ++r) {
-            const std::string pre = "decoder.0.convs." + std::to_string(r + 1);
-            branches.push_back(conv_bn(pre + ".0.weight", pre + ".1", c5, c5c, 256, ah, aw, 3, rates[r]));
-        }
-        {
-            Unit gp; gp.kind = U_GAP; gp.src0 = c5; gp.cout = c5c; gp.hin = ah; gp.win = aw; gp.hout = 1; gp.wout = 1; gp.relu = 0;
-            gp.out = new_act(c5c, 1, 1, false);
-            U.push_back(gp);
-            const int pooled = conv_bn("decoder.0.convs.4.1.weight", "decoder.0.convs.4.2", gp.out, c5c, 256, 1, 1, 1, 0);
-            Unit bc; bc.kind = U_BCAST; bc.src0 = pooled; bc.cout = 256; bc.hin = 1; bc.win = 1; bc.hout = ah; bc.wout = aw; bc.relu = 0;
-            bc.out = new_act(256, ah, aw, false);
-            U.push_back(bc);
-            branches.push_back(bc.out);
-        }
-        Unit cat; cat.kind = U_CONCAT; cat.members = branches; cat.cout = 5 * 256; cat.hout = ah; cat.wout = aw; cat.relu = 0;
-        cat.out = new_act(5 * 256, ah, aw, false);
-        U.push_back(cat);
-        const int proj = conv_bn("decoder.0.project.0.weight", "decoder.0.project.1", cat.out, 5 * 256, 256, ah, aw, 1, 0);
-        Unit dr; dr.kind = U_DROPOUT_E; dr.src0 = proj; dr.cout = 256; dr.hout = ah; dr.wout = aw; dr.relu = 0;
-        dr.out = new_act(256, ah, aw, false);
-        U.push_back(dr);
-        const int fused = conv_bn("decoder.1.weight", "decoder.2", dr.out, 256, 256, ah, aw, 3, 0);
-        xin = fused; xc = 256; head_k = 1; head_h = ah; head_w = aw;
-        net->head_up = 8;
-    }
-    if (net->topology == 4) {
-        // smp.DeepLabV3Plus (decoders/deeplabv3/decoder.py of segmentation-models-pytorch 0.2.1, restated; encoder_output_stride 16:
-        // layer4 dilated above).  aspp = Sequential(ASPP(C5, 256, rates (12, 24, 36), separable), SeparableConv2d(256, 256, 3), BN,
-        // ReLU); ASPP: convs = [1x1 conv + BN + ReLU, 3 x (SeparableConv2d(C5, 256, 3, dilation r) + BN + ReLU), AdaptiveAvgPool2d(1)
-        // + 1x1 conv + BN + ReLU + bilinear back to the map], concat, project = 1x1 conv (1280 -> 256) + BN + ReLU + Dropout(0.5);
-        // up = UpsamplingBilinear2d(4); block1 = 1x1 conv (C2 -> 48) + BN + ReLU on the stride-4 feature; concat; block2 =
-        // SeparableConv2d(304, 256, 3) + BN + ReLU; head = Conv2d(256, classes, 1) + UpsamplingBilinear2d(4).
-        // SeparableConv2d = depthwise 3x3 (dilation = padding) then pointwise 1x1, no norm in between, both without bias.
-        const int c5 = feat[5], c5c = featc[5], ah = A[feat[5]].h, aw = A[feat[5]].w;
-        auto conv_bn = [&](const std::string& wname, const std::string& bnname, int src, int cin, int cout, int hh, int ww) {
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = cout; u.k = 1; u.pad = 0;
-            u.hin = hh; u.win = ww; u.hout = hh; u.wout = ww;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, wname, {cout, cin, 1, 1}, 0);
-            u.bn_idx = add_bn(L, bnname, cout);
-            u.out = new_act(cout, hh, ww, true);
-            U.push_back(u);
-            return u.out;
-        };
-        auto separable_bn = [&](const std::string& pre_conv, const std::string& bnname, int src, int cin, int cout, int hh, int ww, int dil) {
-            Unit d; d.kind = U_DWCONV; d.src0 = src; d.cin0 = cin; d.cout = cin; d.k = 3; d.dil = dil; d.pad = dil; d.relu = 0;
-            d.hin = hh; d.win = ww; d.hout = hh; d.wout = ww;
-            d.w_idx = (int)L.tensors.size(); add_tensor(L, pre_conv + ".0.weight", {cin, 1, 3, 3}, 0);
-            d.out = new_act(cin, hh, ww, false);
-            // the pointwise convolution's weight follows the depthwise one in the state dict, its BatchNorm after both
-            Unit u; u.kind = U_CONV; u.src0 = d.out; u.cin0 = cin; u.cout = cout; u.k = 1; u.pad = 0;
-            u.hin = hh; u.win = ww; u.hout = hh; u.wout = ww;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, pre_conv + ".1.weight", {cout, cin, 1, 1}, 0);
-            u.bn_idx = add_bn(L, bnname, cout);
-            u.out = new_act(cout, hh, ww, true);
-            U.push_back(d); U.push_back(u);
-            return u.out;
-        };
-        std::vector<int> branches;
-        branches.push_back(conv_bn("decoder.aspp.0.convs.0.0.weight", "decoder.aspp.0.convs.0.1", c5, c5c, 256, ah, aw));
-        const int rates[3] = {12, 24, 36};
-        for (int r = 0; r < 3; ++r) {
-            const std::string pre = "decoder.aspp.0.convs." + std::to_string(r + 1);
-            branches.push_back(separable_bn(pre + ".0", pre + ".1", c5, c5c, 256, ah, aw, rates[r]));
-        }
-        {   // ASPPPooling: Sequential(AdaptiveAvgPool2d(1), Conv2d, BatchNorm2d, ReLU) + F.interpolate(size, bilinear, align_corners=False)
-            Unit gp; gp.kind = U_GAP; gp.src0 = c5; gp.cout = c5c; gp.hin = ah; gp.win = aw; gp.hout = 1; gp.wout = 1; gp.relu = 0;
-            gp.out = new_act(c5c, 1, 1, false);
-            U.push_back(gp);
-            const int pooled = conv_bn("decoder.aspp.0.convs.4.1.weight", "decoder.aspp.0.convs.4.2", gp.out, c5c, 256, 1, 1);
-            Unit bc; bc.kind = U_BCAST; bc.src0 = pooled; bc.cout = 256; bc.hin = 1; bc.win = 1; bc.hout = ah; bc.wout = aw; bc.relu = 0;
-            bc.out = new_act(256, ah, aw, false);
-            U.push_back(bc);
-            branches.push_back(bc.out);
-        }
-        Unit cat; cat.kind = U_CONCAT; cat.members = branches; cat.cout = 5 * 256; cat.hout = ah; cat.wout = aw; cat.relu = 0;
-        cat.out = new_act(5 * 256, ah, aw, false);
-        U.push_back(cat);
-        const int proj = conv_bn("decoder.aspp.0.project.0.weight", "decoder.aspp.0.project.1", cat.out, 5 * 256, 256, ah, aw);
-        Unit dr; dr.kind = U_DROPOUT_E; dr.src0 = proj; dr.cout = 256; dr.hout = ah; dr.wout = aw; dr.relu = 0;
-        dr.out = new_act(256, ah, aw, false);
-        U.push_back(dr);
-        const int aspp = separable_bn("decoder.aspp.1", "decoder.aspp.2", dr.out, 256, 256, ah, aw, 1);
-        Unit up; up.kind = U_BILINEAR; up.src0 = aspp; up.cout = 256; up.factor = 4; up.hin = ah; up.win = aw; up.hout = 4 * ah; up.wout = 4 * aw; up.relu = 0;
-        up.out = new_act(256, 4 * ah, 4 * aw, false);
-        U.push_back(up);
-        const Act hr = A[feat[2]];
-        const int high = conv_bn("decoder.block1.0.weight", "decoder.block1.1", feat[2], featc[2], 48, hr.h, hr.w);
-        Unit cat2; cat2.kind = U_CONCAT; cat2.members = {up.out, high}; cat2.cout = 256 + 48; cat2.hout = hr.h; cat2.wout = hr.w; cat2.relu = 0;
-        cat2.out = new_act(256 + 48, hr.h, hr.w, false);
-        U.push_back(cat2);
-        const int fused = separable_bn("decoder.block2.0", "decoder.block2.1", cat2.out, 256 + 48, 256, hr.h, hr.w, 1);
-        xin = fused; xc = 256; head_k = 1; head_h = hr.h; head_w = hr.w;
-        net->head_up = 4;
-    }
-    if (net->topology == 3) {
-        // smp.FPN (decoders/fpn/decoder.py of segmentation-models-pytorch 0.2.1, restated): p5 = Conv1x1(c5); p_k = nearest-x2(p_(k+1)) +
-        // Conv1x1(c_k) for k = 4, 3, 2 (pyramid_channels 256, biased, no norm); seg_blocks[i] on p5, p4, p3, p2 with 3, 2, 1, 0
-        // upsamplings: Conv3x3(256 -> 128, no bias) + GroupNorm(32) + ReLU (+ bilinear x2, align_corners) then (ups - 1) x
-        // [Conv3x3(128 -> 128) + GN + ReLU + bilinear x2]; merge = sum; Dropout2d(0.2); head = Conv1x1(128 -> classes) +
-        // UpsamplingBilinear2d(4).
-        const int pyr = 256, seg = 128;
-        auto lateral = [&](const std::string& name, int src, int cin) {
-            const Act sa = A[src];
-            Unit u; u.kind = U_CONV; u.src0 = src; u.cin0 = cin; u.cout = pyr; u.k = 1; u.pad = 0; u.relu = 0;
-            u.hin = sa.h; u.win = sa.w; u.hout = sa.h; u.wout = sa.w;
-            u.w_idx = (int)L.tensors.size(); add_tensor(L, name + ".weight", {pyr, cin, 1, 1}, 0);
-            u.bias_idx = (int)L.tensors.size(); add_tensor(L, name + ".bias", {pyr}, 3);
-            u.out = new_act(pyr, sa.h, sa.w, false);
-            U.push_back(u);
-            return u.out;
-        };
-        int pyramid[4];
-        pyramid[0] = lateral("decoder.p5", feat[5], featc[5]);
-        for (int k = 0; k < 3; ++k) {   // p4, p3, p2
-            const int lat = lateral("decoder.p" + std::to_string(4 - k) + ".skip_conv", feat[4 - k], featc[4 - k]);
-            const Act la = A[lat];
-            Unit u; u.kind = U_UPADD; u.src0 = pyramid[k]; u.src1 = lat; u.cout = pyr; u.hout = la.h; u.wout = la.w; u.relu = 0;
-            u.hin = la.h / 2; u.win = la.w / 2;
-            u.out = new_act(pyr, la.h, la.w, false);
-            U.push_back(u);
-            pyramid[k + 1] = u.out;
-        }
-        int merged = -1;
-        for (int i = 0; i < 4; ++i) {
-            const int ups = 3 - i;
-            int x_act = pyramid[i], x_c = pyr;
-            for (int j = 0; j < std::max(1, ups); ++j) {
-                const std::string pre = "decoder.seg_blocks." + std::to_string(i) + ".block." + std::to_string(j) + ".block.";
-                const Act xa = A[x_act];
-                Unit u; u.kind = U_CONV; u.src0 = x_act; u.cin0 = x_c; u.cout = seg; u.k = 3; u.pad = 1;
-                u.hin = xa.h; u.win = xa.w; u.hout = xa.h; u.wout = xa.w;
-                u.w_idx = (int)L.tensors.size(); add_tensor(L, pre + "0.weight", {seg, x_c, 3, 3}, 0);
-                u.gn_idx = (int)L.tensors.size(); u.gn_groups = 32;
-                add_tensor(L, pre + "1.weight", {seg}, 1); add_tensor(L, pre + "1.bias", {seg}, 2);
-                u.out = new_act(seg, xa.h, xa.w, true);
-                U.push_back(u);
-                x_act = u.out; x_c = seg;
-                if (ups > 0) {
-                    Unit b; b.kind = U_BILINEAR; b.src0 = x_act; b.cout = seg; b.hin = xa.h; b.win = xa.w; b.hout = 2 * xa.h; b.wout = 2 * xa.w;
-                    b.relu = 0;
-                    b.out = new_act(seg, 2 * xa.h, 2 * xa.w, false);
-                    U.push_back(b);
-                    x_act = b.out;
-                }
-            }
-            if (merged < 0) merged = x_act;
-            else {
-                const Act ma = A[merged];
-                Unit ua; ua.kind = U_ADD; ua.src0 = merged; ua.src1 = x_act; ua.cout = seg; ua.hout = ma.h; ua.wout = ma.w; ua.relu = 0;
-                ua.out = new_act(seg, ma.h, ma.w, false);
-                U.push_back(ua);
-                merged = ua.out;
-            }
-        }
-        {
-            const Act ma = A[merged];
-            Unit d; d.kind = U_DROPOUT; d.src0 = merged; d.cout = seg; d.hout = ma.h; d.wout = ma.w; d.relu = 0;
-            d.out = new_act(seg, ma.h, ma.w, false);
-            U.push_back(d);
-            xin = d.out; xc = seg; head_k = 1; head_h = ma.h; head_w = ma.w;
-            net->head_up = 4;
-        }
-    }
-    if (net->topology == 2) {
-        // smp.Linknet (decoders/linknet/decoder.py of segmentation-models-pytorch 0.2.1, restated): channels = reversed encoder
-        // features (deepest first) + [32]; block i = Conv2dReLU(in, in/4, 1) -> TransposeX2(in/4, in/4) -> Conv2dReLU(in/4, out, 1),
-        // then + skip (the next-shallower encoder feature) for i < 4; head = Conv2d(32, classes, 1).
-        const int chans[6] = {featc[5], featc[4], featc[3], featc[2], featc[1], 32};
-        const int skips[5] = {feat[4], feat[3], feat[2], feat[1], -1};
-        int x_act = feat[5], xh = A[feat[5]].h, xw = A[feat[5]].w;
-        for (int i = 0; i < 5; ++i) {
-            const std::string pre = "decoder.blocks." + std::to_string(i) + ".block.";
-            const int cin = chans[i], mid = cin / 4, cout = chans[i + 1];
-            Unit u1; u1.kind = U_CONV; u1.src0 = x_act; u1.cin0 = cin; u1.cout = mid; u1.k = 1; u1.pad = 0;
-            u1.hin = xh; u1.win = xw; u1.hout = xh; u1.wout = xw;
-            u1.w_idx = (int)L.tensors.size(); add_tensor(L, pre + "0.0.weight", {mid, cin, 1, 1}, 0);
-            u1.bn_idx = add_bn(L, pre + "0.1", mid);
-            u1.out = new_act(mid, xh, xw, true);
-            U.push_back(u1);
-            Unit ut; ut.kind = U_CONVT; ut.src0 = u1.out; ut.cin0 = mid; ut.cout = mid; ut.k = 3; ut.pad = 1;
-            ut.hin = xh; ut.win = xw; ut.hout = 2 * xh; ut.wout = 2 * xw;
-            ut.w_idx = (int)L.tensors.size(); add_tensor(L, pre + "1.0.weight", {mid, mid, 4, 4}, 3);   // torch's [in][out][kh][kw], as is
-            ut.bias_idx = (int)L.tensors.size(); add_tensor(L, pre + "1.0.bias", {mid}, 3);
-            ut.bn_idx = add_bn(L, pre + "1.1", mid);
-            ut.out = new_act(mid, 2 * xh, 2 * xw, true);
-            U.push_back(ut);
-            xh *= 2; xw *= 2;
-            Unit u3; u3.kind = U_CONV; u3.src0 = ut.out; u3.cin0 = mid; u3.cout = cout; u3.k = 1; u3.pad = 0;
-            u3.hin = xh; u3.win = xw; u3.hout = xh; u3.wout = xw;
-            u3.w_idx = (int)L.tensors.size(); add_tensor(L, pre + "2.0.weight", {cout, mid, 1, 1}, 0);
-            u3.bn_idx = add_bn(L, pre + "2.1", cout);
-            u3.out = new_act(cout, xh, xw, true);
-            U.push_back(u3);
-            x_act = u3.out;
-            if (skips[i] >= 0) {
-                Unit ua; ua.kind = U_ADD; ua.src0 = u3.out; ua.src1 = skips[i]; ua.cout = cout; ua.hout = xh; ua.wout = xw; ua.relu = 0;
-                ua.out = new_act(cout, xh, xw, false);
-                U.push_back(ua);
-                x_act = ua.out;
-            }
-        }
-        xin = x_act; xc = 32; head_k = 1;
-    }
-    Unit head; head.kind = U_HEAD; head.src0 = xin; head.cin0 = xc; head.cout = net->classes; head.relu = 0;
-    head.k = head_k; head.pad = head_k / 2;
-    head.hin = head_h; head.win = head_w; head.hout = head_h; head.wout = head_w;
-    head.w_idx = (int)L.tensors.size(); add_tensor(L, "segmentation_head.0.weight", {net->classes, xc, head_k, head_k}, 0);
-    head.bias_idx = (int)L.tensors.size(); add_tensor(L, "segmentation_head.0.bias", {net->classes}, 3);
-    U.push_back(head);
+    net->head_up = x.up;     // the head works at 1 / head_up resolution, nn.UpsamplingBilinear2d(head_up) follows
+    Unit head = Builder::conv(x.act, x.c, net->classes, x.k, 1, B.A[x.act].h, B.A[x.act].w);
+    head.kind = U_HEAD; head.relu = 0;
+    B.attach_weight(head, "segmentation_head.0.weight");
+    B.attach_bias(head, "segmentation_head.0.bias");
+    B.emit(head);
     return VS_OK;
 }
+
+// bytes of a convolution's two prepared weight copies: wc [cout][taps][cin] in the compute dtype and wt, its flipped / transposed twin
+// for the data gradient (grouped layers: 32-channel super-groups; the head's wt pads to 16 output channels; a transposed convolution
+// has the copies of its equivalent 3x3 convolution onto 4 * cout channels).  The same for both weight sets.
+struct WeightCopyBytes { size_t wc, wt; };
+WeightCopyBytes weight_copy_bytes(const Unit& u, size_t esz) {
+    if (u.kind == U_CONVT) return {(size_t)4 * u.cout * 9 * u.cin0 * esz, (size_t)u.cin0 * 9 * 4 * u.cout * esz};
+    const size_t taps = (size_t)u.k * u.k, cin = (size_t)u.cin0 + u.cin1;
+    const size_t cout_pad = u.kind == U_HEAD ? 16 : (size_t)u.cout;
+    return {(size_t)u.cout * taps * (u.cg ? 32 : cin) * esz, cin * taps * (u.cg ? 32 : cout_pad) * esz};
+}
+// the units with fixed-point statistics bins (ConvParams::stats_bins): bias-free convolution + BatchNorm, and the ResNet stem
+bool has_stat_bins(const Unit& u) { return (u.kind == U_CONV && u.bn_idx >= 0 && u.bias_idx < 0) || (u.kind == U_STEM && u.cout == 64); }
 
 size_t plan_workspace(vs_unet* net) {
     const size_t N = (size_t)net->max_batch, esz = net->esz;
@@ -1039,17 +946,12 @@ size_t plan_workspace(vs_unet* net) {
     // weight copies + BN constants
     size_t ct = 0;
     for (auto& u : net->units) {
-        if (u.kind == U_CONV || u.kind == U_HEAD) {
-            const size_t taps = (size_t)u.k * u.k, cin = (size_t)u.cin0 + u.cin1;
-            const size_t cout_pad = u.kind == U_HEAD ? 16 : (size_t)u.cout;
-            u.off_wc = take((size_t)u.cout * taps * (u.cg ? 32 : cin) * esz);
-            u.off_wt = take(cin * taps * (u.cg ? 32 : cout_pad) * esz);
+        if (u.kind == U_CONV || u.kind == U_HEAD || u.kind == U_CONVT) {
+            const WeightCopyBytes b = weight_copy_bytes(u, esz);
+            u.off_wc = take(b.wc);
+            u.off_wt = take(b.wt);
         }
-        if (u.kind == U_CONVT) {   // the equivalent 3x3 convolution onto 4 * cout channels
-            u.off_wc = take((size_t)4 * u.cout * 9 * u.cin0 * esz);
-            u.off_wt = take((size_t)u.cin0 * 9 * 4 * u.cout * esz);
-            ct = std::max(ct, N * u.hin * u.win * 4 * u.cout * esz);
-        }
+        if (u.kind == U_CONVT) ct = std::max(ct, N * u.hin * u.win * 4 * u.cout * esz);
         if (u.bn_idx >= 0) u.off_bn = take(4 * (size_t)u.cout * sizeof(float));
     }
     net->off_ct = take(ct);    // the transposed convolutions' un-shuffled output
@@ -1117,15 +1019,12 @@ size_t plan_workspace(vs_unet* net) {
     {   // fixed-point statistics bins of every convolution + BatchNorm unit (ConvParams::stats_bins): one contiguous block
         size_t total = 0;
         for (auto& u : net->units)
-            if ((u.kind == U_CONV && u.bn_idx >= 0 && u.bias_idx < 0) || (u.kind == U_STEM && u.cout == 64))
-                total += unit_bins_bytes(u.cout) + kTicketBytes;
+            if (has_stat_bins(u)) total += unit_bins_bytes(u.cout) + kTicketBytes;
         net->bins_bytes = total;
         net->off_bins0 = take(total);
         size_t at = net->off_bins0;
         for (auto& u : net->units)
-            if ((u.kind == U_CONV && u.bn_idx >= 0 && u.bias_idx < 0) || (u.kind == U_STEM && u.cout == 64)) {
-                u.off_bins = at; at += unit_bins_bytes(u.cout) + kTicketBytes;
-            }
+            if (has_stat_bins(u)) { u.off_bins = at; at += unit_bins_bytes(u.cout) + kTicketBytes; }
     }
     // activations (a for all, z for conv/stem outputs)
     for (auto& a : net->acts) {
@@ -1136,16 +1035,12 @@ size_t plan_workspace(vs_unet* net) {
     net->ws_eval = off;
     size_t ctdw = 0;
     for (auto& u : net->units) {
-        if (u.kind == U_CONVT) {
-            u.off_wc2 = take((size_t)4 * u.cout * 9 * u.cin0 * esz);
-            u.off_wt2 = take((size_t)u.cin0 * 9 * 4 * u.cout * esz);
-            ctdw = std::max(ctdw, (size_t)4 * u.cout * 9 * u.cin0 * sizeof(float));
-        }
+        if (u.kind == U_CONVT) ctdw = std::max(ctdw, (size_t)4 * u.cout * 9 * u.cin0 * sizeof(float));
         if (u.kind == U_CONV && u.g2) ctdw = std::max(ctdw, (size_t)u.cout * u.k * u.k * u.cin0 * sizeof(float));
-        if (u.kind != U_CONV && u.kind != U_HEAD) continue;
-        const size_t taps = (size_t)u.k * u.k, cin = (size_t)u.cin0 + u.cin1;
-        u.off_wc2 = take((size_t)u.cout * taps * (u.cg ? 32 : cin) * esz);
-        u.off_wt2 = take(cin * taps * (u.cg ? 32 : (u.kind == U_HEAD ? 16 : (size_t)u.cout)) * esz);
+        if (u.kind != U_CONV && u.kind != U_HEAD && u.kind != U_CONVT) continue;
+        const WeightCopyBytes b = weight_copy_bytes(u, esz);
+        u.off_wc2 = take(b.wc);
+        u.off_wt2 = take(b.wt);
     }
     {
         const Unit& hd = net->units.back();
@@ -1206,6 +1101,9 @@ size_t plan_workspace(vs_unet* net) {
     return off;
 }
 
+// the forward reads a prepared copy of the unit's weight, not the fp32 master: low precision, or a layout that only the copy has
+bool has_weight_copy(const vs_unet* net, const Unit& u) { return net->dtype != VS_F32 || u.cg || u.g2; }
+
 struct Ctx {
     vs_unet* net;
     char* ws;
@@ -1220,13 +1118,29 @@ struct Ctx {
     const TensorInfo& t(int idx) const { return net->layout.tensors[idx]; }
     const float* P(int idx) const { return params + t(idx).offset; }
     const void* wfwd(const Unit& u) const {  // weights in the compute dtype
-        return (net->dtype == VS_F32 && !u.cg && !u.g2) ? (const void*)P(u.w_idx) : (const void*)(ws + wc_off(u, net->wset));
+        return has_weight_copy(net, u) ? (const void*)(ws + wc_off(u, net->wset)) : (const void*)P(u.w_idx);
     }
     static size_t wc_off(const Unit& u, int set) { return set ? u.off_wc2 : u.off_wc; }
     static size_t wt_off(const Unit& u, int set) { return set ? u.off_wt2 : u.off_wt; }
     float* bnc(const Unit& u, int which) const { return reinterpret_cast<float*>(ws + u.off_bn) + (size_t)which * u.cout; }
     int64_t rows(const Unit& u) const { return (int64_t)n * u.hout * u.wout; }
 };
+
+// THE weight-copy row of a convolution unit (U_CONV / U_HEAD) in weight set `set`: where its copies go and the shape the copy kernel
+// sees - a large-rate convolution (colr) is the 1x1 convolution over the 9 * cin0 channels of the column form, the head's transposed
+// copy pads to 16 output channels, cg = 255 marks the two-group layout.  wc only where the forward reads a copy (has_weight_copy);
+// want_wt: the flipped / transposed copy of the data gradient; update: the fused optimiser step runs AdamW on the weight.
+WeightCopyRow weight_copy_row(const vs_unet* net, const Unit& u, int set, bool want_wt, bool update) {
+    WeightCopyRow r;
+    r.w_off = net->layout.tensors[u.w_idx].offset;
+    r.wc_off = has_weight_copy(net, u) ? (long)Ctx::wc_off(u, set) : -1;
+    r.wt_off = want_wt ? (long)Ctx::wt_off(u, set) : -1;
+    r.cout = u.cout; r.taps = u.colr ? 1 : u.k * u.k; r.cin = u.colr ? 9 * u.cin0 : u.cin0 + u.cin1;
+    r.cout_pad = u.kind == U_HEAD ? 16 : u.cout;
+    r.cg = u.g2 ? 255 : u.cg;
+    r.update = update;
+    return r;
+}
 
 double conv_flops(const Ctx& c, const Unit& u) {  // algorithmic: 2 * MACs of the (un-padded, un-stuffed) convolution
     return 2.0 * c.n * u.hout * u.wout * (double)u.cout * u.k * u.k * (u.cg ? u.cg : u.cin0 + u.cin1);
@@ -1288,6 +1202,14 @@ WgradParams wgrad_params(const Ctx& c, const Unit& u) {
     return p;
 }
 
+// the standalone BatchNorm unit (U_BN) right behind unit ui that reads its output - EfficientNet's norms, which ride in the epilogue of
+// the convolution in front of them where that can be done - or null
+const Unit* bn_behind(const vs_unet* net, int ui) {
+    if (ui + 1 >= (int)net->units.size()) return nullptr;
+    const Unit& v = net->units[ui + 1];
+    return (v.kind == U_BN && v.src0 == net->units[ui].out) ? &v : nullptr;
+}
+
 // Normalise-on-load (training, bf16): unit ui is a conv -> BN -> ReLU whose output has exactly ONE reader, a stride-1 3x3
 // convolution that takes it as src0 (a BasicBlock's conv1 -> conv2; a decoder block's conv1 -> conv2 -> next block's conv1).
 // Then ui runs no normalisation sweep: its statistics stay in their fixed-point bins, the reader's workgroups sum them in their
@@ -1312,17 +1234,27 @@ int nl_consumer(const Ctx& c, int ui) {
 }  // namespace
 
 // ---- parameter table -------------------------------------------------------------------------------
-static int with_layout(int classes, int encoder_code, Layout& out) {   // encoder_code = topology * 1000 + encoder
+// the (topology, encoder) pairs that are built; encoder_code = topology * 1000 + encoder, `who` heads the message
+static int check_network_code(const char* who, int encoder_code) {
+    const int encoder = encoder_code % 1000, topology = encoder_code / 1000;
+    VS_REQUIRE(topology >= 0 && topology <= 7, "%s: topology must be 0 (U-Net), 1 (U-Net++), 2 (Linknet), 3 (FPN), 4 (DeepLabV3+), 5 (DeepLabV3), 6 (MA-Net) or 7 (PAN), got %d", who, topology);
+    VS_REQUIRE(encoder == 18 || encoder == 34 || encoder == 50 || encoder == 51 || encoder == 103 || encoder == 104 || encoder == 150 || encoder == 201,
+               "%s: encoder must be 18, 34, 50, 51, 103, 104, 150 or 201 (resnet18 / resnet34 / resnet50 / resnext50_32x4d / efficientnet-b3 / "
+               "efficientnet-b4 / timm-resnest50d / timm-resnest101e), got %d", who, encoder);
+    VS_REQUIRE((encoder != 103 && encoder != 104) || topology != 2,
+               "%s: the EfficientNet encoders are not built under smp.Linknet (its decoder narrows 56 / 48 channels to 14 / 12: not multiples of 8)", who);
+    VS_REQUIRE((encoder != 150 && encoder != 201) || (topology != 4 && topology != 5 && topology != 7),
+               "%s: the ResNeSt encoders do not support the dilating decoders (DeepLabV3 / DeepLabV3+ / PAN) - smp's ResNestEncoder.make_dilated "
+               "raises for them as well (their parameter-free average pools would stay at stride 2)", who);
+    return VS_OK;
+}
+
+static int with_layout(int classes, int encoder_code, Layout& out) {
     vs_unet tmp{};
-    const int encoder = encoder_code % 1000;
-    tmp.classes = classes; tmp.h = 64; tmp.w = 64; tmp.max_batch = 1; tmp.dtype = VS_F32; tmp.esz = 4; tmp.encoder = encoder;
-    tmp.topology = encoder_code / 1000;
-    VS_REQUIRE(tmp.topology >= 0 && tmp.topology <= 7, "topology must be 0 (U-Net), 1 (U-Net++), 2 (Linknet), 3 (FPN), 4 (DeepLabV3+), 5 (DeepLabV3), 6 (MA-Net) or 7 (PAN), got %d", tmp.topology);
+    if (check_network_code("unet_tensor_info", encoder_code)) return VS_ERR_INVALID;
     VS_REQUIRE(classes >= 1 && classes <= 16, "classes must be in [1,16], got %d", classes);
-    VS_REQUIRE(encoder == 18 || encoder == 34 || encoder == 50 || encoder == 51 || ((encoder == 103 || encoder == 104) && tmp.topology != 2) ||
-               ((encoder == 150 || encoder == 201) && tmp.topology != 4 && tmp.topology != 5 && tmp.topology != 7),
-               "encoder must be 18, 34, 50, 51 (resnet18 / resnet34 / resnet50 / resnext50_32x4d), 103 / 104 (efficientnet-b3 / b4; not under Linknet) or "
-               "150 / 201 (timm-resnest50d / 101e; not under DeepLabV3(+) / PAN), got %d", encoder_code);
+    tmp.classes = classes; tmp.h = 64; tmp.w = 64; tmp.max_batch = 1; tmp.dtype = VS_F32; tmp.esz = 4;
+    tmp.encoder = encoder_code % 1000; tmp.topology = encoder_code / 1000;
     build(&tmp);
     out = tmp.layout;
     return VS_OK;
@@ -1373,24 +1305,15 @@ extern "C" int vs_unet_create(vs_unet_t** out, int dtype, int classes, int max_b
 
 extern "C" int vs_unet_create_ex(vs_unet_t** out, int dtype, int classes, int max_batch, int h, int w, int encoder_code) {
     VS_REQUIRE(out, "unet_create: null out pointer");
-    const int encoder = encoder_code % 1000, topology = encoder_code / 1000;
-    VS_REQUIRE(topology >= 0 && topology <= 7, "unet_create: topology must be 0 (U-Net), 1 (U-Net++), 2 (Linknet), 3 (FPN), 4 (DeepLabV3+), 5 (DeepLabV3), 6 (MA-Net) or 7 (PAN), got %d", topology);
-    VS_REQUIRE(encoder == 18 || encoder == 34 || encoder == 50 || encoder == 51 || encoder == 103 || encoder == 104 || encoder == 150 || encoder == 201,
-               "unet_create: encoder must be 18, 34, 50, 51, 103, 104, 150 or 201 (resnet18 / resnet34 / resnet50 / resnext50_32x4d / efficientnet-b3 / "
-               "efficientnet-b4 / timm-resnest50d / timm-resnest101e), got %d", encoder);
-    VS_REQUIRE((encoder != 103 && encoder != 104) || topology != 2,
-               "unet_create: the EfficientNet encoders are not built under smp.Linknet (its decoder narrows 56 / 48 channels to 14 / 12: not multiples of 8)");
-    VS_REQUIRE((encoder != 150 && encoder != 201) || (topology != 4 && topology != 5 && topology != 7),
-               "unet_create: the ResNeSt encoders do not support the dilating decoders (DeepLabV3 / DeepLabV3+ / PAN) - smp's ResNestEncoder.make_dilated "
-               "raises for them as well (their parameter-free average pools would stay at stride 2)");
+    if (check_network_code("unet_create", encoder_code)) return VS_ERR_INVALID;
     VS_REQUIRE(dtype == VS_F32 || dtype == VS_BF16 || dtype == VS_F16, "unet_create: bad dtype %d", dtype);
     VS_REQUIRE(classes >= 1 && classes <= 16, "unet_create: classes must be in [1,16], got %d", classes);
     VS_REQUIRE(max_batch >= 1 && h >= 32 && w >= 32 && h % 32 == 0 && w % 32 == 0,
                "unet_create: batch %d, %dx%d - spatial dims must be positive multiples of 32", max_batch, h, w);
     vs_unet* net = new vs_unet();
     net->dtype = dtype; net->classes = classes; net->max_batch = max_batch; net->h = h; net->w = w;
-    net->encoder = encoder;
-    net->topology = topology;
+    net->encoder = encoder_code % 1000;
+    net->topology = encoder_code / 1000;
     net->esz = dtype_size(dtype);
     build(net);
     plan_workspace(net);
@@ -1411,23 +1334,18 @@ extern "C" int vs_unet_prepare(vs_unet_t* net, const float* params, const float*
     ProfScope prof(PK_PREPARE, 0, (double)net->layout.n_params * (4 + net->esz * (training ? 2 : 1)), c.s);
     VS_CHECK_HIP(hipMemsetAsync(c.ws + net->off_bncnt, 0, 256, c.s));   // (the counters re-arm themselves; this covers a fresh workspace)
     {   // every conv layer's low-precision copy and flipped/transposed dgrad copy in one launch
-        long w_off[64], wc_off[64], wt_off[64];
-        int cout[64], taps[64], cin[64], cpad[64], cgs[64], nl = 0;
+        WeightCopyRow rows[64];
+        int nl = 0;
         auto flush = [&]() -> int {
             if (!nl) return VS_OK;
-            const int rc = launch_weight_prepare_all(net->dtype, params, c.ws, nl, w_off, wc_off, wt_off, cout, taps, cin, cpad, cgs, c.s);
+            const int rc = launch_weight_prepare_all(net->dtype, params, c.ws, rows, nl, c.s);
             nl = 0;
             return rc;
         };
         for (auto& u : net->units) {
             if (u.kind != U_CONV && u.kind != U_HEAD) continue;
-            const bool wc = net->dtype != VS_F32 || u.cg || u.g2, wt = training != 0;
-            if (!wc && !wt) continue;
-            cgs[nl] = u.g2 ? 255 : u.cg;
-            w_off[nl] = c.t(u.w_idx).offset;
-            wc_off[nl] = wc ? (long)Ctx::wc_off(u, net->wset) : -1;
-            wt_off[nl] = wt ? (long)Ctx::wt_off(u, net->wset) : -1;
-            cout[nl] = u.cout; taps[nl] = u.colr ? 1 : u.k * u.k; cin[nl] = u.colr ? 9 * u.cin0 : u.cin0 + u.cin1; cpad[nl] = u.kind == U_HEAD ? 16 : u.cout;
+            rows[nl] = weight_copy_row(net, u, net->wset, training != 0, false);
+            if (rows[nl].wc_off < 0 && rows[nl].wt_off < 0) continue;
             if (++nl == 64) {   // the descriptor table of one launch holds 64 layers (U-Net++ / resnet50 has 83)
                 int rc = flush();
                 if (rc) return rc;
@@ -1467,8 +1385,8 @@ extern "C" int vs_unet_prepare(vs_unet_t* net, const float* params, const float*
 extern "C" int vs_unet_prepare_range(vs_unet_t* net, const float* params, void* workspace, void* stream, int unit_lo, int unit_hi) {
     VS_REQUIRE(net && params && workspace && unit_lo >= 0 && unit_lo < unit_hi && unit_hi <= (int)net->units.size(),
                "unet_prepare_range: bad arguments");
-    long w_off[64], wc_off[64], wt_off[64];
-    int cout[64], taps[64], cin[64], cpad[64], cgs[64], nl = 0;
+    WeightCopyRow rows[64];
+    int nl = 0;
     const int other = net->wset ^ 1;
     for (int k = unit_lo; k < unit_hi; ++k) {
         const Unit& v = net->units[k];
@@ -1479,15 +1397,10 @@ extern "C" int vs_unet_prepare_range(vs_unet_t* net, const float* params, void* 
         }
         if (v.kind != U_CONV && v.kind != U_HEAD) continue;
         VS_REQUIRE(nl < 64, "unet_prepare_range: too many layers in one range");
-        w_off[nl] = net->layout.tensors[v.w_idx].offset;
-        wc_off[nl] = (net->dtype != VS_F32 || v.cg || v.g2) ? (long)Ctx::wc_off(v, other) : -1;
-        wt_off[nl] = (long)Ctx::wt_off(v, other);
-        cout[nl] = v.cout; taps[nl] = v.colr ? 1 : v.k * v.k; cin[nl] = v.colr ? 9 * v.cin0 : v.cin0 + v.cin1; cpad[nl] = v.kind == U_HEAD ? 16 : v.cout;
-        cgs[nl] = v.g2 ? 255 : v.cg;
-        ++nl;
+        rows[nl++] = weight_copy_row(net, v, other, true, false);
     }
     if (!nl) return VS_OK;
-    return launch_weight_prepare_all(net->dtype, params, workspace, nl, w_off, wc_off, wt_off, cout, taps, cin, cpad, cgs, (hipStream_t)stream);
+    return launch_weight_prepare_all(net->dtype, params, workspace, rows, nl, (hipStream_t)stream);
 }
 extern "C" int vs_unet_weight_set(const vs_unet_t* net) { return net ? net->wset : VS_ERR_INVALID; }
 // Dropout2d draws of a training forward (smp.FPN): mask = f(seed, *counter) with the counter in device memory (int64; the
@@ -1640,9 +1553,9 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
         }
         case U_DWCONV2: {
             ProfScope prof(PK_POOL_MISC, 0, (double)n * (u.hin * u.win * u.cin0 + u.hout * u.wout * u.cout) * net->esz, c.s);
-            if (!training && !u.bcast && unit_index + 1 < (int)net->units.size() && net->units[unit_index + 1].kind == U_BN &&
-                net->units[unit_index + 1].src0 == u.out && (u.dil == 1 || (u.stride == 1 && (u.dil == 2 || (u.dil == 4 && u.k == 3))))) {
-                const Unit& bn = net->units[unit_index + 1];      // evaluation: its BatchNorm (folded) + swish in the same sweep
+            const Unit* next_bn = bn_behind(net, unit_index);
+            if (!training && !u.bcast && next_bn && (u.dil == 1 || (u.stride == 1 && (u.dil == 2 || (u.dil == 4 && u.k == 3))))) {
+                const Unit& bn = *next_bn;      // evaluation: its BatchNorm (folded) + swish in the same sweep
                 if ((rc = vs_dwconv2d_affine(dt, c.a(u.src0), c.P(u.w_idx), c.bnc(bn, 0), c.bnc(bn, 1), bn.relu, c.a(bn.out), n, u.hin, u.win, u.cout, u.k,
                                              u.stride, u.pad, u.dil, u.hout, u.wout, stream))) return rc;
                 bn_folded_into_conv = true;
@@ -1806,8 +1719,8 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
             if (u.bn_idx < 0 && u.gn_idx < 0) {   // plain biased convolution (FPN's lateral 1x1s): no norm, no activation
                 p.out = c.a(u.out); p.shift = u.bias_idx >= 0 ? c.P(u.bias_idx) : nullptr;   // (EfficientNet's 1x1 convolutions: no bias either)
                 // its BatchNorm is the next unit (U_BN): the batch statistics come straight from the fp32 accumulators, as for the fused units
-                if (training && dt == VS_BF16 && u.bias_idx < 0 && unit_index + 1 < (int)net->units.size() &&
-                    net->units[unit_index + 1].kind == U_BN && net->units[unit_index + 1].src0 == u.out) {
+                const Unit* next_bn = bn_behind(net, unit_index);
+                if (training && dt == VS_BF16 && u.bias_idx < 0 && next_bn) {
                     const int rows_needed = plan.stat_rows;
                     if (rows_needed > 0 && (size_t)rows_needed * 2 * u.cout * sizeof(float) <= net->bnws_bytes) {
                         p.stats_partial = (float*)(c.ws + net->off_bnws);
@@ -1815,9 +1728,8 @@ static int unet_forward(vs_unet_t* net, const float* params, float* bnstate, con
                     }
                 }
                 // evaluation: the BatchNorm unit behind it (folded running statistics) and its activation ride in this epilogue
-                if (!training && u.bias_idx < 0 && unit_index + 1 < (int)net->units.size() && net->units[unit_index + 1].kind == U_BN &&
-                    net->units[unit_index + 1].src0 == u.out) {
-                    const Unit& bn = net->units[unit_index + 1];
+                if (!training && u.bias_idx < 0 && next_bn) {
+                    const Unit& bn = *next_bn;
                     p.scale = c.bnc(bn, 0); p.shift = c.bnc(bn, 1); p.relu = bn.relu; p.out = c.a(bn.out);
                     bn_folded_into_conv = true;
                 }
@@ -2015,8 +1927,8 @@ static int update_units(const Ctx& c, int lo, int hi, bool need_encoder_wgrad, c
     const int dt = net->dtype;
     const int other = net->wset ^ 1;
     AdamwRanges r{};
-    long w_off[64], wc_off[64], wt_off[64];
-    int cout[64], taps[64], cin[64], cpad[64], cgs[64], upd[64], nl = 0;
+    WeightCopyRow rows[64];
+    int nl = 0;
     int rc;
     // Per range of units: ONE launch steps the small tensors (BatchNorm affine parameters, biases, the stem, depthwise / attention
     // tensors: ranges of the flat buffers), ONE launch steps the convolution weights INSIDE the derivation of their copies for the next
@@ -2024,7 +1936,7 @@ static int update_units(const Ctx& c, int lo, int hi, bool need_encoder_wgrad, c
     auto flush = [&]() -> int {
         int rc2;
         if (r.n && (rc2 = launch_adamw_ranges(opt, grads, r, s))) return rc2;
-        if (nl && (rc2 = launch_adamw_prepare_all(dt, opt, grads, c.ws, nl, w_off, wc_off, wt_off, cout, taps, cin, cpad, cgs, upd, s))) return rc2;
+        if (nl && (rc2 = launch_adamw_prepare_all(dt, opt, grads, c.ws, rows, nl, s))) return rc2;
         r.n = 0; nl = 0;
         return VS_OK;
     };
@@ -2047,15 +1959,7 @@ static int update_units(const Ctx& c, int lo, int hi, bool need_encoder_wgrad, c
         if (v.bn_idx >= 0 && aux_on) { push(v.bn_idx); push(v.bn_idx + 1); }
         if (v.gn_idx >= 0) { push(v.gn_idx); push(v.gn_idx + 1); }
         if (v.bias_idx >= 0 && aux_on) push(v.bias_idx);
-        if (v.kind == U_CONV || v.kind == U_HEAD) {
-            w_off[nl] = c.t(v.w_idx).offset;
-            wc_off[nl] = (dt != VS_F32 || v.cg || v.g2) ? (long)Ctx::wc_off(v, other) : -1;
-            wt_off[nl] = (long)Ctx::wt_off(v, other);
-            cout[nl] = v.cout; taps[nl] = v.colr ? 1 : v.k * v.k; cin[nl] = v.colr ? 9 * v.cin0 : v.cin0 + v.cin1; cpad[nl] = v.kind == U_HEAD ? 16 : v.cout;
-            cgs[nl] = v.g2 ? 255 : v.cg;
-            upd[nl] = !(v.frozen_candidate && !need_encoder_wgrad);
-            ++nl;
-        }
+        if (conv_w) rows[nl++] = weight_copy_row(net, v, other, true, !(v.frozen_candidate && !need_encoder_wgrad));
     }
     if ((rc = flush())) return rc;
     for (int k = lo; k < hi; ++k) {   // transposed convolutions: their own expansion kernel, after every AdamW launch of the range
@@ -2779,4 +2683,70 @@ extern "C" int vs_unet_debug_unit(const vs_unet_t* net, int unit, char* wname, i
     const Act& a = net->acts[u.out];
     *c = a.c; *h = a.h; *w = a.w; *off_a = a.off_a; *off_z = a.off_z; *off_da = a.off_da; *off_dz = a.off_dz;
     return VS_OK;
+}
+
+// ---- plan dump -------------------------------------------------------------------------------------
+// The whole plan as line-oriented text, every value as name=value: one header line, one line per tensor, per activation and per
+// unit, with EVERY member of Unit (also those a kind never reads; floats as %a).  Host only; it reads and nothing else.  Two builds
+// construct the same plans exactly when their dumps are equal byte for byte (tools/unet_plan_sweep.py, tests/test_host_logic.py).
+extern "C" size_t vs_unet_plan_dump(const vs_unet_t* net, char* buf, size_t cap) {
+    if (!net) return 0;
+    std::string s;
+    char tmp[160];
+    auto I = [&](const char* name, long long v) { snprintf(tmp, sizeof tmp, " %s=%lld", name, v); s += tmp; };
+    auto Z = [&](const char* name, size_t v) { snprintf(tmp, sizeof tmp, " %s=%zu", name, v); s += tmp; };
+    auto F = [&](const char* name, float v) { snprintf(tmp, sizeof tmp, " %s=%a", name, (double)v); s += tmp; };
+    auto list = [&](const char* name, const std::vector<int>& v) {
+        s += " "; s += name; s += "=[";
+        for (size_t i = 0; i < v.size(); ++i) { if (i) s += ","; s += std::to_string(v[i]); }
+        s += "]";
+    };
+    s += "plan";
+    I("dtype", net->dtype); I("classes", net->classes); I("max_batch", net->max_batch); I("h", net->h); I("w", net->w);
+    I("topology", net->topology); I("encoder", net->encoder); I("head_up", net->head_up); Z("esz", net->esz);
+    I("n_params", net->layout.n_params); I("n_bnstate", net->layout.n_bnstate); Z("ws_eval", net->ws_eval); Z("ws_train", net->ws_train);
+    Z("off_bins0", net->off_bins0); Z("bins_bytes", net->bins_bytes); Z("off_bnws", net->off_bnws); Z("bnws_bytes", net->bnws_bytes);
+    Z("off_wgws", net->off_wgws); Z("wgws_bytes", net->wgws_bytes); Z("off_headdw", net->off_headdw); Z("off_headpart", net->off_headpart);
+    Z("off_dyh", net->off_dyh); Z("off_dup", net->off_dup); Z("off_zs", net->off_zs); Z("off_idx", net->off_idx);
+    Z("off_logits", net->off_logits); Z("off_bncnt", net->off_bncnt); Z("off_syncsc", net->off_syncsc); Z("off_gnz", net->off_gnz);
+    Z("off_gnws", net->off_gnws); Z("gnws_bytes", net->gnws_bytes); Z("off_dropmask", net->off_dropmask); Z("off_lsmall", net->off_lsmall);
+    Z("off_dlsmall", net->off_dlsmall); Z("off_pab", net->off_pab); Z("pab_bytes", net->pab_bytes); Z("off_sews", net->off_sews);
+    Z("off_gapws", net->off_gapws); Z("gapws_bytes", net->gapws_bytes); Z("off_avgw9", net->off_avgw9); Z("off_avgw4", net->off_avgw4);
+    I("avgw_c", net->avgw_c); Z("off_ys", net->off_ys); Z("off_ct", net->off_ct); Z("off_ctdw", net->off_ctdw); Z("ctdw_bytes", net->ctdw_bytes);
+    s += "\n";
+    for (size_t i = 0; i < net->layout.tensors.size(); ++i) {
+        const TensorInfo& t = net->layout.tensors[i];
+        s += "tensor";
+        I("index", (long long)i); s += " name=" + t.name; I("ndim", t.ndim);
+        s += " shape=[";
+        for (int d = 0; d < 4; ++d) { if (d) s += ","; s += std::to_string(t.shape[d]); }
+        s += "]";
+        I("kind", t.kind); I("offset", t.offset);
+        s += "\n";
+    }
+    for (size_t i = 0; i < net->acts.size(); ++i) {
+        const Act& a = net->acts[i];
+        s += "act";
+        I("index", (long long)i); I("c", a.c); I("h", a.h); I("w", a.w); I("has_z", a.has_z);
+        Z("off_a", a.off_a); Z("off_z", a.off_z); Z("off_da", a.off_da); Z("off_dz", a.off_dz);
+        s += "\n";
+    }
+    for (size_t i = 0; i < net->units.size(); ++i) {
+        const Unit& u = net->units[i];
+        s += "unit";
+        I("index", (long long)i); I("kind", u.kind); I("src0", u.src0); I("src1", u.src1); I("up0", u.up0);
+        I("cin0", u.cin0); I("cin1", u.cin1); I("cout", u.cout); I("k", u.k); I("stride", u.stride); I("pad", u.pad);
+        I("hin", u.hin); I("win", u.win); I("hout", u.hout); I("wout", u.wout);
+        I("w_idx", u.w_idx); I("bn_idx", u.bn_idx); I("bias_idx", u.bias_idx); I("out", u.out); I("res", u.res); I("relu", u.relu);
+        I("gn_idx", u.gn_idx); I("gn_groups", u.gn_groups); Z("off_gn", u.off_gn); F("bn_eps", u.bn_eps); F("bn_mom", u.bn_mom);
+        F("drop_p", u.drop_p); I("salt", u.salt); I("bcast", u.bcast); I("g2", u.g2); I("aux_frozen", u.aux_frozen); F("pool_w", u.pool_w);
+        I("dil", u.dil); I("factor", u.factor); I("colr", u.colr); Z("off_xs", u.off_xs); I("cg", u.cg);
+        I("frozen_candidate", u.frozen_candidate); Z("off_wc", u.off_wc); Z("off_wt", u.off_wt); Z("off_bn", u.off_bn);
+        Z("off_bins", u.off_bins); Z("off_wc2", u.off_wc2); Z("off_wt2", u.off_wt2); list("tens", u.tens);
+        Z("off_fpa_pool", u.off_fpa_pool); Z("off_fpa_arena", u.off_fpa_arena); Z("off_fpa_plane", u.off_fpa_plane);
+        list("members", u.members);
+        s += "\n";
+    }
+    if (buf && cap) memcpy(buf, s.data(), std::min(cap, s.size()));
+    return s.size();
 }
