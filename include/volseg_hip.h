@@ -619,6 +619,30 @@ int vs_augment_batch(const uint8_t* images, const uint8_t* masks, int n, int siz
                      void* workspace, size_t workspace_bytes, float* fields_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training feed from resident volumes: the fitted slice pairs of data/datasets.py:fit_to_square (LongestMaxSize + centred
+ * PadIfNeeded) cut out of the uint8 data / label volumes in device memory - no PNG slices, no fitted copies per axis
+ * ---------------------------------------------------------------------------------------- */
+/* One sample = one slice of one volume.  Pixel (y, x) of the slice lies at img_off + y * row_stride + x * col_stride of the data
+ * buffer and at msk_off + (the same) of the label buffer (elements).  nh, nw, top, left and border are fit_to_square's own
+ * numbers, computed by the host (data/volume_feed.py); the kernel does not re-derive them. */
+typedef struct vs_slice_cut {
+    int64_t img_off, msk_off;          /* first pixel of the slice in the data / label buffer */
+    int64_t row_stride, col_stride;
+    int32_t h, w;                      /* the slice as it lies in the volume */
+    int32_t nh, nw;                    /* after LongestMaxSize(size) (== h, w: the slice is copied, not resampled) */
+    int32_t top, left;                 /* centred pad: output pixel (y, x) is padded-slice pixel (y - top, x - left) */
+    int32_t border;                    /* np.pad mode: 0 "reflect" (reflect-101, periodic), 1 "edge" */
+    int32_t reserved;
+} vs_slice_cut;
+/* images / masks (n, size, size) uint8 = the fitted pairs of the n descriptors in table_dev (device memory; any mix of volumes,
+ * axes and indices, repeats included), bit for bit what fit_to_square gives for the same slices: image bilinear (cv2.resize
+ * INTER_LINEAR coordinates, fp32, round half to even), mask nearest (floor(dst * scale)).  data_elems / label_elems: sizes of the
+ * two buffers; a descriptor that would read outside them reads nothing and its pair comes out zero (callers validate their
+ * table on the host).  size: a multiple of 4; n <= 65535. */
+int vs_slices_cut_u8(const uint8_t* data, int64_t data_elems, const uint8_t* labels, int64_t label_elems,
+                     const vs_slice_cut* table_dev, int n, int size, uint8_t* images, uint8_t* masks, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Volume pre-processing (BaseDataManager._preprocess_data, data/base_data_manager.py:29-42;
  * clip_to_uint8, utilities/base_data_utils.py:243-287)
  * ---------------------------------------------------------------------------------------- */

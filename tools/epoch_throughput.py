@@ -1,7 +1,8 @@
 """End-to-end `VolSeg2dTrainer.train_model` epoch throughput on a synthetic 256^3 volume (needs a GPU): the volume and its labels
 go through TrainingDataSlicer (PNG slices along all three axes, as `model-train-2d` does), then epochs are timed with (a) the
-reference's feed - every PNG decoded again in every epoch by 4 DataLoader workers, batches augmented on the device - and (b) the
-resident feed (slices decoded once, kept as uint8 in HBM).  Prints slices/s per epoch next to the bare training step's rate.
+reference's feed - every PNG decoded again in every epoch by 4 DataLoader workers, batches augmented on the device - (b) the
+resident feed (slices decoded once, kept as uint8 in HBM) and (c) the volume feed (no PNGs: the uint8 volumes resident once, every
+batch cut out of them on the device - data/volume_feed.py).  Prints slices/s per epoch next to the bare training step's rate.
     python tools/epoch_throughput.py [cube=256] [epochs=3] [batch=32]"""
 import logging
 import pathlib
@@ -39,9 +40,13 @@ def main():
     n_slices = len(list((root / "data").glob("*.png")))
     print(f"sliced {n_slices} PNG pairs in {time.perf_counter() - t0:.1f} s")
     results = {}
-    for name, resident in (("PNG decode per epoch, 4 workers", False), ("resident uint8 slices in HBM", True)):
+    for name, resident in (("PNG decode per epoch, 4 workers", False), ("resident uint8 slices in HBM", True),
+                           ("volume feed: slices cut from the resident volumes", None)):
         settings.resident_feed = resident
-        trainer = VolSeg2dTrainer(root / "data", root / "seg", slicer.num_seg_classes, settings)
+        if resident is None:
+            trainer = VolSeg2dTrainer.from_volumes([slicer], slicer.num_seg_classes, settings)
+        else:
+            trainer = VolSeg2dTrainer(root / "data", root / "seg", slicer.num_seg_classes, settings)
         steps = len(trainer.training_loader)
         times = []
         orig = logging.info
@@ -51,7 +56,7 @@ def main():
             return orig(msg, *a, **k)
         logging.info = spy
         try:
-            trainer.train_model(root / f"model_{int(resident)}.pytorch", epochs, patience=epochs + 1, create=True, frozen=False)
+            trainer.train_model(root / f"model_{len(results)}.pytorch", epochs, patience=epochs + 1, create=True, frozen=False)
         finally:
             logging.info = orig
         per_epoch = n_slices            # training steps + the validation pass see every slice once per epoch

@@ -241,6 +241,7 @@ _SIGS = {
     "vs_keys_unpack": (I, [P, P, P, I64, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
+    "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),
     "vs_volume_sum_workspace": (SZ, [I64]),
     "vs_volume_sum": (I, [I, P, I64, I, C.c_double, P, SZ, P, P]),
     "vs_clip_to_uint8": (I, [I, P, I64, C.c_double, C.c_double, C.c_double, P, P, P]),

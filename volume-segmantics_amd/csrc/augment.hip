@@ -14,29 +14,10 @@
 // Sampling = cv2.remap semantics: bilinear in fp32, BORDER_REFLECT_101, result rounded to uint8 after every stage (the
 // library resamples stage by stage too).  data/augmentations.py is the NumPy form of the same arithmetic (host path + tests).
 #include "common.h"
+#include "resample.h"      // refl101, sample_bilinear: shared with the slice feed (slice_feed.hip)
 
 namespace {
 
-__device__ __forceinline__ int refl101(int i, int n) {
-    if (n == 1) return 0;
-    const int period = 2 * (n - 1);
-    i %= period;
-    if (i < 0) i += period;
-    return i >= n ? period - i : i;
-}
-
-// bilinear sample of an (h x w) uint8 image at (sx, sy), reflect-101 outside, rounded half-to-even like np.rint
-__device__ __forceinline__ uint8_t sample_bilinear(const uint8_t* img, int pitch, int h, int w, float sx, float sy) {
-    const float x0f = floorf(sx), y0f = floorf(sy);
-    const float fx = sx - x0f, fy = sy - y0f;
-    const int x0 = (int)x0f, y0 = (int)y0f;
-    const int xa = refl101(x0, w), xb = refl101(x0 + 1, w), ya = refl101(y0, h), yb = refl101(y0 + 1, h);
-    const float a = img[ya * pitch + xa], b = img[ya * pitch + xb], c = img[yb * pitch + xa], d = img[yb * pitch + xb];
-    const float top = __fadd_rn(__fmul_rn(a, 1.f - fx), __fmul_rn(b, fx));
-    const float bot = __fadd_rn(__fmul_rn(c, 1.f - fx), __fmul_rn(d, fx));
-    const float v = __fadd_rn(__fmul_rn(top, 1.f - fy), __fmul_rn(bot, fy));
-    return (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
-}
 __device__ __forceinline__ uint8_t sample_nearest(const uint8_t* img, int pitch, int h, int w, float sx, float sy) {
     return img[refl101((int)rintf(sy), h) * pitch + refl101((int)rintf(sx), w)];
 }

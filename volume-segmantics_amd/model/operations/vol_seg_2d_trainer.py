@@ -77,6 +77,31 @@ class VolSeg2dTrainer:
         self.model_struc_dict = self._get_model_struc_dict(settings)
         self.avg_train_losses, self.avg_valid_losses, self.avg_eval_scores = [], [], []
 
+    @classmethod
+    def from_volumes(cls, slicers, labels: Union[int, dict], settings: SimpleNamespace, png_dirs=None):
+        """The trainer fed straight from the volumes of ``slicers`` (TrainingDataSlicer objects, in the order the train command
+        numbers them): no PNG slices are written, the uint8 volumes are uploaded once and every batch is cut out of them on
+        the device (data/volume_feed.py).  Sample numbering, split, samplers and batches are those of the PNG route.  Where the
+        volumes do not fit the feed's share of device memory - on any rank - the slices are written to ``png_dirs`` =
+        (data directory, label directory) after all and the PNG route is taken."""
+        from ...data.volume_feed import get_volume_training_loaders
+        slicers = list(slicers)
+        vdist.init_from_env()
+        rank, world = vdist.world()
+        loaders = get_volume_training_loaders(slicers, settings, rank, world)
+        if loaders is not None:
+            return cls(None, None, labels, settings, loaders=loaders)
+        if png_dirs is None:
+            raise RuntimeError("the training volumes do not fit the volume feed's share of device memory and no png_dirs were given "
+                               "for the PNG route")
+        data_dir, seg_dir = png_dirs
+        if rank == 0:
+            for count, slicer in enumerate(slicers):
+                slicer.output_data_slices(data_dir, f"data{count}")
+                slicer.output_label_slices(seg_dir, f"seg{count}")
+        vdist.barrier()
+        return cls(data_dir, seg_dir, labels, settings)
+
     # ---- construction helpers -------------------------------------------------------------------------------
     def _get_model_struc_dict(self, settings):
         d = settings.model     # (the reference fills in the caller's dict too, vol_seg_2d_trainer.py:78-84)

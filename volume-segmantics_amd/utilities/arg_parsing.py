@@ -1,0 +1,76 @@
+"""Command lines of the two commands (scripts/train_2d_model.py, scripts/predict_2d_model.py), with the reference's arguments:
+
+    train:    --data FILE [FILE ...] --labels FILE [FILE ...] [--data_dir DIR]
+    predict:  MODEL FILE [--data_dir DIR]
+
+``--data_dir`` (default: the working directory) holds ``volseg-settings/`` and receives every output.  A volume or model file
+with a suffix the engine does not read, or one that does not exist, is a usage error (argparse: exit status 2)."""
+from __future__ import annotations
+
+import argparse
+import logging
+import sys
+from datetime import date
+from pathlib import Path
+
+from . import config as cfg
+
+
+def existing_file_with_suffix(suffixes):
+    """argparse ``type``: the path, refused unless its suffix is one of ``suffixes`` and the file exists."""
+    allowed = sorted(suffixes)
+
+    def convert(text: str) -> Path:
+        path = Path(text)
+        if path.suffix not in suffixes:
+            raise argparse.ArgumentTypeError(f"wrong file type: {path} does not end with one of {allowed}")
+        if not path.is_file():
+            raise argparse.ArgumentTypeError(f"the file {path} does not appear to exist")
+        return path
+    return convert
+
+
+def _add_data_dir(parser: argparse.ArgumentParser) -> None:
+    parser.add_argument("--" + cfg.DATA_DIR_ARG, type=Path, default=None, metavar="DIR",
+                        help=f'directory that holds "{cfg.SETTINGS_DIR}/" and receives the outputs (default: the working directory)')
+
+
+def get_2d_training_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Train a 2d segmentation model on 3d data volume(s) and their label volume(s).")
+    parser.add_argument("--" + cfg.TRAIN_DATA_ARG, type=existing_file_with_suffix(cfg.TRAIN_DATA_EXT), nargs="+", required=True,
+                        metavar="FILE", help="imaging data volume(s) to train on")
+    parser.add_argument("--" + cfg.LABEL_DATA_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), nargs="+", required=True,
+                        metavar="FILE", help="segmented label volume(s), one per data volume, in the same order")
+    _add_data_dir(parser)
+    return parser
+
+
+def get_2d_prediction_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Segment a 3d data volume with a trained 2d model.")
+    parser.add_argument(cfg.MODEL_PTH_ARG, type=existing_file_with_suffix(cfg.MODEL_DATA_EXT), metavar="MODEL",
+                        help="trained model file (.pytorch / .pth)")
+    parser.add_argument(cfg.PREDICT_DATA_ARG, type=existing_file_with_suffix(cfg.PREDICT_DATA_EXT), metavar="FILE",
+                        help="imaging data volume to segment")
+    _add_data_dir(parser)
+    return parser
+
+
+def root_path(args: argparse.Namespace) -> Path:
+    given = getattr(args, cfg.DATA_DIR_ARG)
+    return (Path.cwd() if given is None else Path(given)).resolve()
+
+
+def check_volume_counts(data_vols, label_vols) -> None:
+    if len(data_vols) != len(label_vols):
+        logging.error("Number of data volumes and number of label volumes must be equal!")
+        sys.exit(1)
+
+
+def model_output_path(root: Path, model_type_name: str, model_output_fn: str, today: date | None = None) -> Path:
+    """<date>_<type>_<model_output_fn>.pytorch under ``root``."""
+    return Path(root) / f"{today or date.today()}_{model_type_name}_{model_output_fn}.pytorch"
+
+
+def prediction_output_path(root: Path, data_vol_path: Path, today: date | None = None) -> Path:
+    """<date>_<stem of the data file>_2d_model_vol_pred.h5 under ``root``."""
+    return Path(root) / f"{today or date.today()}_{Path(data_vol_path).stem}_2d_model_vol_pred.h5"
