@@ -716,6 +716,18 @@ int vs_merge_maxprob(uint8_t* label0, uint16_t* prob0, const uint8_t* label1, co
                      int64_t n, void* stream);
 int vs_keys_unpack(const uint32_t* keys, uint8_t* labels, uint16_t* probs, int64_t n, void* stream);
 
+/* Confusion matrix of a predicted label volume against ground truth (utilities/evaluation.py scores from it): for every slab
+ * of slab_len consecutive voxels (nslabs = ceil(n / slab_len); slab_len = n: the whole volume, slab_len = H * W: one matrix
+ * per leading-axis slice; slab boundaries need not be multiples of 16 bytes, the two volume bases must be)
+ * counts[slab][t][p] = voxels whose truth maps to class t and whose prediction is p.  truth_lut (256 device bytes, or NULL)
+ * maps a raw ground-truth byte to its class; entry 255 = ignore the voxel, 254 = invalid.  NULL = identity, every byte
+ * >= classes invalid.  A voxel whose truth is ignored goes to dropped[slab][0]; one whose truth is invalid or >= classes, or
+ * whose prediction is >= classes, to dropped[slab][1]; neither is counted anywhere else.  1 <= classes <= 16 (above:
+ * VS_ERR_INVALID).  counts ([nslabs][classes][classes]) and dropped ([nslabs][2]) are zeroed by the call; the sums are
+ * integer, so the result is the same bits on every run. */
+int vs_confusion_matrix(const uint8_t* truth, const uint8_t* pred, int64_t n, int classes, const uint8_t* truth_lut,
+                        int64_t slab_len, int64_t* counts, int64_t* dropped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

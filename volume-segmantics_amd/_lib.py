@@ -239,6 +239,7 @@ _SIGS = {
     "vs_unet_forward_to_volume": (I, [P, P, P, P, I, P, P, C.POINTER(DirMap), I, I, I, P, P, P, P, I64]),
     "vs_merge_maxprob": (I, [P, P, P, P, I64, P]),
     "vs_keys_unpack": (I, [P, P, P, I64, P]),
+    "vs_confusion_matrix": (I, [P, P, I64, I, P, I64, P, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

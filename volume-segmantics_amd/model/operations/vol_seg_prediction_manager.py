@@ -1,5 +1,6 @@
 """VolSeg2DPredictionManager - volume in, label volume out / to disk
 (reference: volume_segmantics/model/operations/vol_seg_prediction_manager.py:12-100)."""
+import logging
 from pathlib import Path
 from types import SimpleNamespace
 from typing import Union
@@ -52,3 +53,47 @@ class VolSeg2DPredictionManager(BaseDataManager):
                 # the reference hard-codes the name: "<stem>_probs.h5" whatever the label file's suffix (:94-98)
                 utils.save_data_to_hdf5(probs, f"{output_path.parent / output_path.stem}_probs.h5", chunking=self.input_data_chunking)
         return prediction
+
+    def evaluate_volume(self, label_vol: Union[Path, str, np.ndarray], output_path: Union[Path, None] = None,
+                        quality: Union[utils.Quality, None] = None, prediction: Union[np.ndarray, None] = None):
+        """Score the segmentation of the data volume against the labelled volume ``label_vol`` (a path or an array): per-class
+        Dice / IoU / precision / recall, voxel accuracy and the confusion matrix (utilities/evaluation.py).  Predicts through
+        ``predict_volume_to_path`` unless ``prediction`` is given.  With ``output_path`` the label volume is written as usual and
+        beside it ``<stem>_scores.csv``, ``<stem>_scores.json`` and, with the settings key ``evaluation_per_slice: true``,
+        ``<stem>_scores_per_slice.csv``.  Class ``i`` is the ``i``-th ground-truth value in ascending order, from the checkpoint's
+        label codes where they record the values (evaluation.truth_label_values); ``evaluation_ignore_label`` sets voxels aside.
+        Returns the scores; ``last_evaluation`` keeps the prediction, the dropped counts and the per-slice Dice."""
+        from ... import dist as vdist
+        from ...utilities import evaluation as ev
+
+        if self.settings.one_hot:
+            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there is nothing to score "
+                             "(set one_hot: False to evaluate)")
+        if isinstance(label_vol, (str, Path)):
+            truth, _ = utils.get_numpy_from_path(Path(label_vol), internal_path=getattr(self.settings, "seg_hdf5_path", self.settings.data_hdf5_path))
+        elif isinstance(label_vol, np.ndarray):
+            truth = label_vol
+        else:
+            raise TypeError("label_vol must be a path or a numpy array")
+        expected = tuple(self.data_vol.shape if prediction is None else prediction.shape)
+        if expected != tuple(truth.shape):
+            why = " (downsample: True halves the data volume before it is predicted: the labels must be of that size)" if self.downsample else ""
+            raise ValueError(f"the prediction has shape {expected} but the label volume has shape {tuple(truth.shape)}{why}")
+        rank0 = vdist.world()[0] == 0       # under torch.distributed every rank that holds the merged volume scores it; rank 0 writes
+        if prediction is None:
+            prediction = self.predict_volume_to_path(output_path if rank0 else None, quality)
+        if prediction is None:        # a rank that does not hold the merged volume (predictor.result_ranks = "rank0")
+            return None
+        classes = int(self.predictor.num_labels)
+        ignore = getattr(self.settings, "evaluation_ignore_label", None)
+        per_slice = bool(getattr(self.settings, "evaluation_per_slice", False))
+        values = ev.truth_label_values(self.get_label_codes(), truth, classes, ignore_label=ignore)
+        device = f"cuda:{self.predictor.model_device_num}"
+        scores, dropped, slab_dice = ev.evaluate_label_volumes(prediction, truth, classes, label_values=values, ignore_label=ignore,
+                                                               per_slice=per_slice, device=device)
+        self.last_evaluation = {"prediction": prediction, "dropped": dropped, "per_slice_dice": slab_dice, "label_values": values}
+        logging.info("Scores against the label volume:\n" + ev.score_table(scores, values))
+        if output_path is not None and rank0:
+            output_path = Path(output_path)
+            ev.write_scores(output_path.parent / output_path.stem, scores, dropped, values, slab_dice)
+        return scores

@@ -1,7 +1,9 @@
-"""Command lines of the two commands (scripts/train_2d_model.py, scripts/predict_2d_model.py), with the reference's arguments:
+"""Command lines of the commands (scripts/train_2d_model.py, scripts/predict_2d_model.py, scripts/evaluate_2d_model.py); the first two
+take the reference's arguments:
 
     train:    --data FILE [FILE ...] --labels FILE [FILE ...] [--data_dir DIR]
     predict:  MODEL FILE [--data_dir DIR]
+    evaluate: MODEL FILE --labels LABELS [--data_dir DIR]   |   --prediction PRED --labels LABELS [--data_dir DIR]
 
 ``--data_dir`` (default: the working directory) holds ``volseg-settings/`` and receives every output.  A volume or model file
 with a suffix the engine does not read, or one that does not exist, is a usage error (argparse: exit status 2)."""
@@ -53,6 +55,35 @@ def get_2d_prediction_parser() -> argparse.ArgumentParser:
                         help="imaging data volume to segment")
     _add_data_dir(parser)
     return parser
+
+
+def get_2d_evaluation_parser() -> argparse.ArgumentParser:
+    """MODEL FILE --labels LABELS predicts and scores; --prediction PRED --labels LABELS scores an existing label volume."""
+    parser = argparse.ArgumentParser(description="Score a segmentation against a labelled volume: predict with a trained 2d model "
+                                                 "and score the result, or score an existing label volume (--prediction).")
+    parser.add_argument(cfg.MODEL_PTH_ARG, type=existing_file_with_suffix(cfg.MODEL_DATA_EXT), metavar="MODEL", nargs="?", default=None,
+                        help="trained model file (.pytorch / .pth)")
+    parser.add_argument(cfg.PREDICT_DATA_ARG, type=existing_file_with_suffix(cfg.PREDICT_DATA_EXT), metavar="FILE", nargs="?", default=None,
+                        help="imaging data volume to segment")
+    parser.add_argument("--" + cfg.LABEL_DATA_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), required=True, metavar="LABELS",
+                        help="labelled (ground-truth) volume to score against")
+    parser.add_argument("--" + cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), default=None, metavar="PRED",
+                        help="an existing predicted label volume to score instead of predicting (takes no MODEL / FILE)")
+    _add_data_dir(parser)
+    return parser
+
+
+def parse_evaluation_args(argv=None) -> argparse.Namespace:
+    """The evaluate command's arguments; exactly one of (MODEL and FILE) or --prediction, anything else is a usage error (exit 2)."""
+    parser = get_2d_evaluation_parser()
+    args = parser.parse_args(argv)
+    model, data = getattr(args, cfg.MODEL_PTH_ARG), getattr(args, cfg.PREDICT_DATA_ARG)
+    if getattr(args, cfg.PREDICTION_ARG) is not None:
+        if model is not None or data is not None:
+            parser.error("--prediction scores an existing label volume: give no MODEL or FILE with it")
+    elif model is None or data is None:
+        parser.error("give MODEL and FILE to predict and score, or --prediction PRED to score an existing label volume")
+    return args
 
 
 def root_path(args: argparse.Namespace) -> Path:

@@ -6,6 +6,7 @@ HDF5_SUFFIXES = {".h5", ".hdf5", ".nxs"}
 NUMPY_SUFFIXES = {".npy"}  # extension of this engine: raw arrays, no third-party I/O library needed
 TRAIN_DATA_EXT = LABEL_DATA_EXT = PREDICT_DATA_EXT = HDF5_SUFFIXES | TIFF_SUFFIXES | NUMPY_SUFFIXES
 MODEL_DATA_EXT = {".pytorch", ".pth"}
+PREDICTION_ARG = "prediction"  # evaluate command: an existing label volume to score (extension of this engine)
 LOGGING_FMT = "%(asctime)s - %(levelname)s - %(message)s"
 LOGGING_DATE_FMT = "%d-%b-%y %H:%M:%S"
 SETTINGS_DIR = "volseg-settings"
