@@ -728,6 +728,28 @@ int vs_keys_unpack(const uint32_t* keys, uint8_t* labels, uint16_t* probs, int64
 int vs_confusion_matrix(const uint8_t* truth, const uint8_t* pred, int64_t n, int classes, const uint8_t* truth_lut,
                         int64_t slab_len, int64_t* counts, int64_t* dropped, void* stream);
 
+/* ---- surface distances (csrc/surface.hip) ----
+ * Z x Y x X uint8 volumes, x fastest.  The surface of a voxel set M is every voxel of M with one of its six face neighbours not
+ * in M; a neighbour outside the volume is not in M, and an axis of length 1 has no neighbours (it is skipped, so a 1 x H x W
+ * volume has 2-D surfaces).
+ *
+ * vs_label_surface: surface[v] = 1 where the class of labels[v] is cls and v is on the surface of that class, 0 elsewhere.  lut
+ * (256 device bytes, or NULL = identity) maps a raw byte to its class as in vs_confusion_matrix; entries 254 / 255 never equal
+ * cls (0 <= cls <= 253).  count (or NULL) receives the number of surface voxels.  Both volumes 16-byte aligned. */
+int vs_label_surface(const uint8_t* labels, const uint8_t* lut, int cls, int64_t Z, int64_t Y, int64_t X, uint8_t* surface,
+                     int64_t* count, void* stream);
+/* vs_edt_squared: d2[v] = the exact squared Euclidean distance (unit voxels) from v to the nearest non-zero voxel of seeds;
+ * 0xFFFFFFFF everywhere when there is none.  Integer arithmetic throughout: the same bits on every run.  The extents must
+ * satisfy (Z-1)^2 + (Y-1)^2 + (X-1)^2 < 2^32 - 1 (otherwise VS_ERR_INVALID).  workspace: vs_edt_workspace_bytes(Z, Y, X) bytes
+ * of device memory (0 while neither Y nor Z exceeds the 512 positions a workgroup's LDS tile holds; NULL is then accepted). */
+size_t vs_edt_workspace_bytes(int64_t Z, int64_t Y, int64_t X);
+int vs_edt_squared(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, uint32_t* d2, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* vs_surface_distance_histogram: hist[min(d2[v], bins - 1)] += 1 for every v < n with from_surface[v] != 0.  hist (bins int64)
+ * is zeroed by the call; integer sums, the same bits in any arrival order.  from_surface 4-byte, d2 16-byte aligned. */
+int vs_surface_distance_histogram(const uint8_t* from_surface, const uint32_t* d2, int64_t n, int64_t bins, int64_t* hist,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,7 +62,10 @@ class VolSeg2DPredictionManager(BaseDataManager):
         beside it ``<stem>_scores.csv``, ``<stem>_scores.json`` and, with the settings key ``evaluation_per_slice: true``,
         ``<stem>_scores_per_slice.csv``.  Class ``i`` is the ``i``-th ground-truth value in ascending order, from the checkpoint's
         label codes where they record the values (evaluation.truth_label_values); ``evaluation_ignore_label`` sets voxels aside.
-        Returns the scores; ``last_evaluation`` keeps the prediction, the dropped counts and the per-slice Dice."""
+        Returns the scores; ``last_evaluation`` keeps the prediction, the dropped counts and the per-slice Dice.  With the settings key
+        ``evaluation_surface_distances: true`` the surface distances (utilities/surface_distance.py: Hausdorff, its 95th percentile,
+        average symmetric surface distance, surface Dice at ``evaluation_surface_tolerance``, distances in ``evaluation_voxel_size``) are
+        computed as well, logged, written to ``<stem>_surface_scores.csv`` / ``.json`` and kept in ``last_evaluation["surface_scores"]``."""
         from ... import dist as vdist
         from ...utilities import evaluation as ev
 
@@ -96,4 +99,9 @@ class VolSeg2DPredictionManager(BaseDataManager):
         if output_path is not None and rank0:
             output_path = Path(output_path)
             ev.write_scores(output_path.parent / output_path.stem, scores, dropped, values, slab_dice)
+        from ...utilities import surface_distance as sd
+        if sd.surface_settings(self.settings)[0]:
+            stem = output_path.parent / output_path.stem if output_path is not None and rank0 else None
+            self.last_evaluation["surface_scores"] = sd.evaluate_surface_distances(
+                prediction, truth, classes, self.settings, label_values=values, ignore_label=ignore, device=device, stem=stem)[0]
         return scores

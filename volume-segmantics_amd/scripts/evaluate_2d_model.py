@@ -8,7 +8,8 @@ The first form reads ``DIR/volseg-settings/2d_model_predict_settings.yaml``, pre
 an existing label volume (one the reference wrote, for instance) and also runs on a host without a GPU; the class count is then the
 number of distinct values over both files, class ``i`` being the ``i``-th of them in ascending order.  Both log the per-class table
 and write ``<stem>_scores.csv`` and ``<stem>_scores.json`` beside the prediction's name under ``DIR`` (``<stem>_scores_per_slice.csv``
-too with the settings key ``evaluation_per_slice: true``)."""
+too with the settings key ``evaluation_per_slice: true``; ``<stem>_surface_scores.csv`` and ``<stem>_surface_scores.json`` - Hausdorff
+distances, average symmetric surface distance, surface Dice - with ``evaluation_surface_distances: true``)."""
 from __future__ import annotations
 
 import logging
@@ -41,6 +42,10 @@ def _score_existing(root, pred_path, labels_path, settings) -> None:
                                                            per_slice=bool(getattr(settings, "evaluation_per_slice", False)))
     logging.info("Scores against the label volume:\n" + ev.score_table(scores, values))
     ev.write_scores(root / pred_path.stem, scores, dropped, values, slab_dice)
+    from ..utilities import surface_distance as sd
+    if sd.surface_settings(settings)[0]:
+        sd.evaluate_surface_distances(pred_classes, truth, len(values), settings, label_values=values, ignore_label=ignore,
+                                      stem=root / pred_path.stem)
 
 
 def main(argv=None) -> None:
