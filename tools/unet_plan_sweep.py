@@ -27,7 +27,7 @@ DEFAULT_OPTIONS = dict(   # csrc/prof.hip: g_opts
     side_stream=1, conv_direct=1, conv_nw8=1, conv_ring=1, conv_stream=1, wgrad_ring=1, wgrad_xcd=1, stats_bins=1, fuse_bn_bwd=1, nl_fwd=1,
     stem_bf16=1, conv_pair=1, conv_min_wgs=512, conv_nw8_min_wgs=128, conv_direct_min_px=262144, conv_direct_rows=32,
     conv_direct_rows_big=128, conv_ring_max_wgs=1024, conv_stream_min_tiles=2, wgrad_target=96, wgrad_target_plain=256, wgrad_slab_mb=16,
-    fork_every=2, bn_inline_rows=64, nl_max_c=64)
+    fork_every=2, bn_inline_rows=64, nl_max_c=64, bn_prefetch=1)
 
 
 _BUF = C.create_string_buffer(1 << 20)   # one dump fits (the largest of the sweep is under 0.4 MB); a larger one is asked for again

@@ -7,6 +7,7 @@
 // biased variance for normalisation, unbiased variance for the running estimate.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "prof.h"
@@ -40,6 +41,48 @@ RowMap make_rowmap(int64_t rows, int c, int max_blocks = 0) {
     int64_t ipb = (iters + nb - 1) / nb;
     m.rows_per_block = ipb * m.rpb;
     return m;
+}
+
+// ---- prefetched first trip (the `bn_prefetch` option, PF forms of the sweeps below) ----------------------------------------------
+// A deep-layer workgroup runs exactly one trip, and in front of it up to two more dependent memory rounds: the statistics rows it
+// sums itself, then the per-channel parameters.  None of the trip's row loads depends on those, so the PF forms issue them (and the
+// parameter loads) first and keep the rows in their storage format across the prologue: three round trips become one.  A plain
+// __syncthreads() is a bare s_barrier here (no LDS-DMA in flight): ordinary loads stay in flight across it.
+// 8 consecutive elements in their storage format (4 registers for the 16-bit types) until they are used: unpack8(ld8raw(p)) is ld8(p)
+template <typename T> struct Raw8 { uint4 u; };
+template <> struct Raw8<float> { float4 a, b; };
+template <typename T> __device__ __forceinline__ Raw8<T> ld8raw(const T* p) { return Raw8<T>{*reinterpret_cast<const uint4*>(p)}; }
+template <> __device__ __forceinline__ Raw8<float> ld8raw<float>(const float* p) { return Raw8<float>{ld4(p), ld4(p + 4)}; }
+__device__ __forceinline__ void unpack8(const Raw8<bf16_t>& r, float* o) {
+    o[0] = __uint_as_float(r.u.x << 16); o[1] = __uint_as_float(r.u.x & 0xffff0000u);
+    o[2] = __uint_as_float(r.u.y << 16); o[3] = __uint_as_float(r.u.y & 0xffff0000u);
+    o[4] = __uint_as_float(r.u.z << 16); o[5] = __uint_as_float(r.u.z & 0xffff0000u);
+    o[6] = __uint_as_float(r.u.w << 16); o[7] = __uint_as_float(r.u.w & 0xffff0000u);
+}
+__device__ __forceinline__ void unpack8(const Raw8<f16_t>& r, float* o) {
+    const float2 a = unpack_f16(r.u.x), b = unpack_f16(r.u.y), c = unpack_f16(r.u.z), d = unpack_f16(r.u.w);
+    o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y; o[4] = c.x; o[5] = c.y; o[6] = d.x; o[7] = d.y;
+}
+__device__ __forceinline__ void unpack8(const Raw8<float>& r, float* o) {
+    o[0] = r.a.x; o[1] = r.a.y; o[2] = r.a.z; o[3] = r.a.w; o[4] = r.b.x; o[5] = r.b.y; o[6] = r.b.z; o[7] = r.b.w;
+}
+// four statistics of partial row r (zeros past the last row) by an UNCONDITIONAL load: a row past the end re-reads row `fb` and is
+// masked afterwards - around a conditional load hipcc branches and waits, one dependent round per row instead of one per four rows
+__device__ __forceinline__ float4 partial_row4(const float* __restrict__ partial, int r, int fb, int nparts, int stride, int col) {
+    const float4 t = *reinterpret_cast<const float4*>(partial + (size_t)(r < nparts ? r : fb) * stride + col * 4);
+    return r < nparts ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// element offsets of the kU rows of the trip that starts at row rb: a row past r1 re-reads row `fb` (an existing one) and is masked
+// at use.  The row loops pass fb = rb; the prefetch, which runs before anything is known to be in range, passes live = false for a
+// thread without a first row (idle lane, empty or ragged block) and reads row 0 - no thread ever forms an out-of-range address.
+__device__ __forceinline__ void trip_offsets(int64_t rb, int64_t r1, bool live, int rpb, int c, int cvi, size_t (&o)[kU], bool (&ok)[kU]) {
+    const int64_t fb = live ? rb : 0;
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+        const int64_t r = rb + (int64_t)u * rpb;
+        ok[u] = live && r < r1;
+        o[u] = (size_t)(ok[u] ? r : fb) * c + cvi * kVec;
+    }
 }
 
 // ---- forward statistics ------------------------------------------------------------------------
@@ -196,7 +239,9 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
 // Workgroup 0 also publishes mean / invstd for the backward pass and updates the running statistics.
 // FIXED: `partial` holds nparts rows of 64-bit fixed-point bins ([row][2][c]: sum x * 2^24, sum x^2 * 2^16, accumulated by atomic adds
 // in the producing convolution's epilogue - ConvParams::stats_bins) instead of fp32 partial rows
-template <typename T, bool FIXED = false>
+// PF: the first trip's rows (x, residual) and gamma / beta are loaded BEFORE the statistics prologue (see Raw8 above); PF = false is
+// the reference form of tests/test_hip_bn_prefetch.py and the other arm of the A/B (option bn_prefetch)
+template <typename T, bool FIXED = false, bool PF = false>
 __global__ __launch_bounds__(256) void bn_apply_inline_kernel(const T* __restrict__ x, const float* __restrict__ partial, int nparts,
                                                             float eps, float momentum, float* __restrict__ mean,
                                                             float* __restrict__ invstd, float* __restrict__ running_mean,
@@ -205,6 +250,24 @@ __global__ __launch_bounds__(256) void bn_apply_inline_kernel(const T* __restric
                                                             T* __restrict__ y, int64_t rows, int c, RowMap m, int64_t stat_rows = 0) {
     extern __shared__ float s_stat[];   // [2][c]: mean, invstd
     const int tid = threadIdx.x;
+    Raw8<T> px[PF ? kU : 1], pr[PF ? kU : 1];
+    float pg[PF ? kVec : 1], pb[PF ? kVec : 1];
+    if constexpr (PF) {
+        const int cvi = tid % m.cv, rl = tid / m.cv;
+        const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
+        const int64_t r1 = min(rows, r0 + m.rows_per_block);
+        size_t o[kU];
+        bool ok[kU];
+        trip_offsets(r0 + rl, r1, rl < m.rpb && r0 + rl < r1, m.rpb, c, cvi, o, ok);
+#pragma unroll
+        for (int u = 0; u < kU; ++u) px[u] = ld8raw(x + o[u]);
+        if (res) {
+#pragma unroll
+            for (int u = 0; u < kU; ++u) pr[u] = ld8raw(res + o[u]);
+        }
+#pragma unroll
+        for (int k = 0; k < kVec; ++k) { pg[k] = gamma[cvi * kVec + k]; pb[k] = beta[cvi * kVec + k]; }
+    }
     if (stat_rows <= 0) stat_rows = rows;        // (the sums may describe more rows than this rank sweeps: cross-rank statistics)
     auto finish = [&](int ch, double s, double q) {
         const double mu = s / (double)stat_rows;
@@ -264,8 +327,10 @@ __global__ __launch_bounds__(256) void bn_apply_inline_kernel(const T* __restric
         for (int r = rg; r < nparts; r += 4 * RG) {
             float4 v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                v[u] = (r + u * RG < nparts) ? *reinterpret_cast<const float4*>(partial + (size_t)(r + u * RG) * 2 * c + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int u = 0; u < 4; ++u) {
+                if constexpr (PF) v[u] = partial_row4(partial, r + u * RG, r, nparts, 2 * c, col);
+                else v[u] = (r + u * RG < nparts) ? *reinterpret_cast<const float4*>(partial + (size_t)(r + u * RG) * 2 * c + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u) { a0 += (double)v[u].x; a1 += (double)v[u].y; a2 += (double)v[u].z; a3 += (double)v[u].w; }
         }
@@ -291,46 +356,105 @@ __global__ __launch_bounds__(256) void bn_apply_inline_kernel(const T* __restric
     __syncthreads();
     const int cvi = tid % m.cv, rl = tid / m.cv;
     if (rl >= m.rpb) return;
-    float a[kVec], b[kVec], mu[kVec];
+    if constexpr (PF) {
+        const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
+        const int64_t r1 = min(rows, r0 + m.rows_per_block);
+        float a[kVec], b[kVec], mu[kVec];
 #pragma unroll
-    for (int k = 0; k < kVec; ++k) {
-        const int ch = cvi * kVec + k;
-        a[k] = s_stat[c + ch] * gamma[ch];
-        b[k] = beta[ch];
-        mu[k] = s_stat[ch];
-    }
-    const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
-    const int64_t r1 = min(rows, r0 + m.rows_per_block);
-    // kU rows per trip with every load issued before the first use: one 16-byte load in flight per thread left these sweeps
-    // latency-bound at ~2.5 TB/s (a trip per ~1 us memory round trip)
-    for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)kU * m.rpb) {
-        float v[kU][kVec], rv[kU][kVec];
-        size_t o[kU];
-        bool ok[kU];
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int64_t r = rb + (int64_t)u * m.rpb;
-            ok[u] = r < r1;
-            o[u] = (size_t)(ok[u] ? r : rb) * c + cvi * kVec;
-            ld8(x + o[u], v[u]);
+        for (int k = 0; k < kVec; ++k) {
+            const int ch = cvi * kVec + k;
+            a[k] = s_stat[c + ch] * pg[k];
+            b[k] = pb[k];
+            mu[k] = s_stat[ch];
         }
-        if (res) {
+        auto finish_trip = [&](float (&v)[kU][kVec], const float (&rv)[kU][kVec], const size_t (&o)[kU], const bool (&ok)[kU]) {
 #pragma unroll
-            for (int u = 0; u < kU; ++u) ld8(res + o[u], rv[u]);
-        }
+            for (int u = 0; u < kU; ++u) {
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
+                for (int k = 0; k < kVec; ++k) v[u][k] = (v[u][k] - mu[k]) * a[k] + b[k];
+                if (res) {
 #pragma unroll
-            for (int k = 0; k < kVec; ++k) v[u][k] = (v[u][k] - mu[k]) * a[k] + b[k];
+                    for (int k = 0; k < kVec; ++k) v[u][k] += rv[u][k];
+                }
+                if (relu) {
+#pragma unroll
+                    for (int k = 0; k < kVec; ++k) v[u][k] = fmaxf(v[u][k], 0.f);
+                }
+                if (ok[u]) st8(y + o[u], v[u]);
+            }
+        };
+        int64_t rb = r0 + rl;
+        {      // trip 0 from the prefetched registers
+            float v[kU][kVec], rv[kU][kVec];
+            size_t o[kU];
+            bool ok[kU];
+            trip_offsets(rb, r1, rb < r1, m.rpb, c, cvi, o, ok);
+#pragma unroll
+            for (int u = 0; u < kU; ++u) unpack8(px[u], v[u]);
             if (res) {
 #pragma unroll
-                for (int k = 0; k < kVec; ++k) v[u][k] += rv[u][k];
+                for (int u = 0; u < kU; ++u) unpack8(pr[u], rv[u]);
             }
-            if (relu) {
+            finish_trip(v, rv, o, ok);
+            rb += (int64_t)kU * m.rpb;
+        }
+        // kU rows per trip with every load issued before the first use: one 16-byte load in flight per thread left these sweeps
+        // latency-bound at ~2.5 TB/s (a trip per ~1 us memory round trip)
+        for (; rb < r1; rb += (int64_t)kU * m.rpb) {
+            float v[kU][kVec], rv[kU][kVec];
+            size_t o[kU];
+            bool ok[kU];
+            trip_offsets(rb, r1, true, m.rpb, c, cvi, o, ok);
 #pragma unroll
-                for (int k = 0; k < kVec; ++k) v[u][k] = fmaxf(v[u][k], 0.f);
+            for (int u = 0; u < kU; ++u) ld8(x + o[u], v[u]);
+            if (res) {
+#pragma unroll
+                for (int u = 0; u < kU; ++u) ld8(res + o[u], rv[u]);
             }
-            if (ok[u]) st8(y + o[u], v[u]);
+            finish_trip(v, rv, o, ok);
+        }
+    } else {     // the form without the prefetch, as it always was
+        float a[kVec], b[kVec], mu[kVec];
+#pragma unroll
+        for (int k = 0; k < kVec; ++k) {
+            const int ch = cvi * kVec + k;
+            a[k] = s_stat[c + ch] * gamma[ch];
+            b[k] = beta[ch];
+            mu[k] = s_stat[ch];
+        }
+        const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
+        const int64_t r1 = min(rows, r0 + m.rows_per_block);
+        // kU rows per trip with every load issued before the first use: one 16-byte load in flight per thread left these sweeps
+        // latency-bound at ~2.5 TB/s (a trip per ~1 us memory round trip)
+        for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)kU * m.rpb) {
+            float v[kU][kVec], rv[kU][kVec];
+            size_t o[kU];
+            bool ok[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int64_t r = rb + (int64_t)u * m.rpb;
+                ok[u] = r < r1;
+                o[u] = (size_t)(ok[u] ? r : rb) * c + cvi * kVec;
+                ld8(x + o[u], v[u]);
+            }
+            if (res) {
+#pragma unroll
+                for (int u = 0; u < kU; ++u) ld8(res + o[u], rv[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+#pragma unroll
+                for (int k = 0; k < kVec; ++k) v[u][k] = (v[u][k] - mu[k]) * a[k] + b[k];
+                if (res) {
+#pragma unroll
+                    for (int k = 0; k < kVec; ++k) v[u][k] += rv[u][k];
+                }
+                if (relu) {
+#pragma unroll
+                    for (int k = 0; k < kVec; ++k) v[u][k] = fmaxf(v[u][k], 0.f);
+                }
+                if (ok[u]) st8(y + o[u], v[u]);
+            }
         }
     }
 }
@@ -417,7 +541,9 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize(const float* __restrict__
 // bn_bwd_finalize forms); workgroup 0 publishes dgamma / dbeta.  One launch and one dependent phase fewer per unit.
 // BINS (with INLINE): `partial` holds nparts rows of 64-bit fixed-point bins ([row][2][c], sums scaled by kBwdStatScale, added
 // atomically by the dgrad epilogue that completed the gradient - ConvParams::bstats_bins): integer sums, any order, same bits.
-template <typename T, bool RECOMPUTE, bool INLINE = false, bool BINS = false>
+// PF: the first trip's rows (dy, x, y) and mean / invstd / gamma / beta are loaded before the prologue (INLINE: the partial-row or bin
+// sum; otherwise the dbeta / dgamma loads and their products), and the `relu` test sits outside the row loop
+template <typename T, bool RECOMPUTE, bool INLINE = false, bool BINS = false, bool PF = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, const T* __restrict__ y,
                                                   const T* __restrict__ x, const float* __restrict__ mean,
                                                   const float* __restrict__ invstd, const float* __restrict__ gamma,
@@ -426,6 +552,31 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, co
                                                   T* __restrict__ dres, int64_t rows, int c, RowMap m,
                                                   const float* __restrict__ partial = nullptr, int nparts = 0, int64_t stat_rows = 0) {
     const int tid = threadIdx.x;
+    constexpr int NY = RECOMPUTE ? 1 : kU;
+    Raw8<T> pdy[PF ? kU : 1], px[PF ? kU : 1], py[PF ? NY : 1];
+    float pmu[PF ? kVec : 1], pis[PF ? kVec : 1], pga[PF ? kVec : 1], pbe[PF && RECOMPUTE ? kVec : 1];
+    if constexpr (PF) {
+        const int cvi = tid % m.cv, rl = tid / m.cv;
+        const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
+        const int64_t r1 = min(rows, r0 + m.rows_per_block);
+        size_t o[kU];
+        bool ok[kU];
+        trip_offsets(r0 + rl, r1, rl < m.rpb && r0 + rl < r1, m.rpb, c, cvi, o, ok);
+#pragma unroll
+        for (int u = 0; u < kU; ++u) { pdy[u] = ld8raw(dy + o[u]); px[u] = ld8raw(x + o[u]); }
+        if constexpr (!RECOMPUTE) {
+            if (relu) {
+#pragma unroll
+                for (int u = 0; u < kU; ++u) py[u] = ld8raw(y + o[u]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kVec; ++k) {
+            const int ch = cvi * kVec + k;
+            pmu[k] = mean[ch]; pis[k] = invstd[ch]; pga[k] = gamma[ch];
+            if constexpr (RECOMPUTE) pbe[k] = beta[ch];
+        }
+    }
     __shared__ float s_coef[INLINE ? 2 * 512 : 1];
     if constexpr (INLINE && BINS) {
         __shared__ long long isum[256];
@@ -465,8 +616,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, co
         for (int r = rg; r < nparts; r += 4 * RG) {
             float4 v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                v[u] = (r + u * RG < nparts) ? *reinterpret_cast<const float4*>(partial + (size_t)(r + u * RG) * 2 * c + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int u = 0; u < 4; ++u) {
+                if constexpr (PF) v[u] = partial_row4(partial, r + u * RG, r, nparts, 2 * c, col);
+                else v[u] = (r + u * RG < nparts) ? *reinterpret_cast<const float4*>(partial + (size_t)(r + u * RG) * 2 * c + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u) { a0 += (double)v[u].x; a1 += (double)v[u].y; a2 += (double)v[u].z; a3 += (double)v[u].w; }
         }
@@ -484,49 +637,116 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, co
     const int cvi = tid % m.cv, rl = tid / m.cv;
     if (rl >= m.rpb) return;
     const float inv_m = 1.0f / (float)(stat_rows > 0 ? stat_rows : rows);   // (stat_rows: the sums cover the rows of every rank)
-    float mu[kVec], is[kVec], gi[kVec], db[kVec], dg[kVec], be[RECOMPUTE ? kVec : 1], ga[RECOMPUTE ? kVec : 1];
+    if constexpr (PF) {
+        const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
+        const int64_t r1 = min(rows, r0 + m.rows_per_block);
+        float mu[kVec], is[kVec], gi[kVec], db[kVec], dg[kVec], be[RECOMPUTE ? kVec : 1], ga[RECOMPUTE ? kVec : 1];
 #pragma unroll
-    for (int k = 0; k < kVec; ++k) {
-        const int ch = cvi * kVec + k;
-        mu[k] = mean[ch]; is[k] = invstd[ch]; gi[k] = gamma[ch] * invstd[ch];
-        if constexpr (INLINE) { db[k] = s_coef[ch] * inv_m; dg[k] = s_coef[c + ch] * inv_m; }
-        else { db[k] = dbeta[ch] * inv_m; dg[k] = dgamma[ch] * inv_m; }
-        if constexpr (RECOMPUTE) { be[k] = beta[ch]; ga[k] = invstd[ch] * gamma[ch]; }
-    }
-    const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
-    const int64_t r1 = min(rows, r0 + m.rows_per_block);
-    for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)kU * m.rpb) {
-        float g[kU][kVec], xv[kU][kVec], yv[RECOMPUTE ? 1 : kU][kVec];
-        size_t o[kU];
-        bool ok[kU];
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int64_t r = rb + (int64_t)u * m.rpb;
-            ok[u] = r < r1;
-            o[u] = (size_t)(ok[u] ? r : rb) * c + cvi * kVec;
-            ld8(dy + o[u], g[u]);
-            ld8(x + o[u], xv[u]);
-            if constexpr (!RECOMPUTE) {
-                if (relu) ld8(y + o[u], yv[u]);
-            }
+        for (int k = 0; k < kVec; ++k) {
+            const int ch = cvi * kVec + k;
+            mu[k] = pmu[k]; is[k] = pis[k]; gi[k] = pga[k] * pis[k];
+            if constexpr (INLINE) { db[k] = s_coef[ch] * inv_m; dg[k] = s_coef[c + ch] * inv_m; }
+            else { db[k] = dbeta[ch] * inv_m; dg[k] = dgamma[ch] * inv_m; }
+            if constexpr (RECOMPUTE) { be[k] = pbe[k]; ga[k] = pis[k] * pga[k]; }
         }
+        // the sweep in two versions, with and without the ReLU mask: a `relu` test inside the unrolled row loop makes hipcc branch
+        // around every y load and wait for each one (four dependent rounds per trip instead of one)
+        auto sweep = [&](auto relu_c) {
+            constexpr bool RELU = decltype(relu_c)::value;
+            auto finish_trip = [&](float (&g)[kU][kVec], const float (&xv)[kU][kVec], const float (&yv)[NY][kVec], const size_t (&o)[kU], const bool (&ok)[kU]) {
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            if (!ok[u]) continue;
-            if (relu) {
+                for (int u = 0; u < kU; ++u) {
+                    if (!ok[u]) continue;
+                    if constexpr (RELU && !RECOMPUTE) {
+#pragma unroll
+                        for (int k = 0; k < kVec; ++k) g[u][k] = yv[u][k] > 0.f ? g[u][k] : 0.f;
+                    } else if constexpr (RELU) {
+#pragma unroll
+                        for (int k = 0; k < kVec; ++k) g[u][k] = ((xv[u][k] - mu[k]) * ga[k] + be[k]) > 0.f ? g[u][k] : 0.f;
+                    }
+                    if (dres) st8(dres + o[u], g[u]);
+                    float o8[kVec];
+#pragma unroll
+                    for (int k = 0; k < kVec; ++k) o8[k] = gi[k] * (g[u][k] - db[k] - (xv[u][k] - mu[k]) * is[k] * dg[k]);
+                    st8(dx + o[u], o8);
+                }
+            };
+            int64_t rb = r0 + rl;
+            {      // trip 0 from the prefetched registers
+                float g[kU][kVec], xv[kU][kVec], yv[NY][kVec];
+                size_t o[kU];
+                bool ok[kU];
+                trip_offsets(rb, r1, rb < r1, m.rpb, c, cvi, o, ok);
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    unpack8(pdy[u], g[u]);
+                    unpack8(px[u], xv[u]);
+                    if constexpr (RELU && !RECOMPUTE) unpack8(py[u], yv[u]);
+                }
+                finish_trip(g, xv, yv, o, ok);
+                rb += (int64_t)kU * m.rpb;
+            }
+            for (; rb < r1; rb += (int64_t)kU * m.rpb) {
+                float g[kU][kVec], xv[kU][kVec], yv[NY][kVec];
+                size_t o[kU];
+                bool ok[kU];
+                trip_offsets(rb, r1, true, m.rpb, c, cvi, o, ok);
+#pragma unroll
+                for (int u = 0; u < kU; ++u) {
+                    ld8(dy + o[u], g[u]);
+                    ld8(x + o[u], xv[u]);
+                    if constexpr (RELU && !RECOMPUTE) ld8(y + o[u], yv[u]);
+                }
+                finish_trip(g, xv, yv, o, ok);
+            }
+        };
+        if (relu) sweep(std::true_type{});
+        else sweep(std::false_type{});
+    } else {     // the form without the prefetch, as it always was
+        float mu[kVec], is[kVec], gi[kVec], db[kVec], dg[kVec], be[RECOMPUTE ? kVec : 1], ga[RECOMPUTE ? kVec : 1];
+#pragma unroll
+        for (int k = 0; k < kVec; ++k) {
+            const int ch = cvi * kVec + k;
+            mu[k] = mean[ch]; is[k] = invstd[ch]; gi[k] = gamma[ch] * invstd[ch];
+            if constexpr (INLINE) { db[k] = s_coef[ch] * inv_m; dg[k] = s_coef[c + ch] * inv_m; }
+            else { db[k] = dbeta[ch] * inv_m; dg[k] = dgamma[ch] * inv_m; }
+            if constexpr (RECOMPUTE) { be[k] = beta[ch]; ga[k] = invstd[ch] * gamma[ch]; }
+        }
+        const int64_t r0 = (int64_t)blockIdx.x * m.rows_per_block;
+        const int64_t r1 = min(rows, r0 + m.rows_per_block);
+        for (int64_t rb = r0 + rl; rb < r1; rb += (int64_t)kU * m.rpb) {
+            float g[kU][kVec], xv[kU][kVec], yv[RECOMPUTE ? 1 : kU][kVec];
+            size_t o[kU];
+            bool ok[kU];
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int64_t r = rb + (int64_t)u * m.rpb;
+                ok[u] = r < r1;
+                o[u] = (size_t)(ok[u] ? r : rb) * c + cvi * kVec;
+                ld8(dy + o[u], g[u]);
+                ld8(x + o[u], xv[u]);
                 if constexpr (!RECOMPUTE) {
-#pragma unroll
-                    for (int k = 0; k < kVec; ++k) g[u][k] = yv[u][k] > 0.f ? g[u][k] : 0.f;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < kVec; ++k) g[u][k] = ((xv[u][k] - mu[k]) * ga[k] + be[k]) > 0.f ? g[u][k] : 0.f;
+                    if (relu) ld8(y + o[u], yv[u]);
                 }
             }
-            if (dres) st8(dres + o[u], g[u]);
-            float o8[kVec];
 #pragma unroll
-            for (int k = 0; k < kVec; ++k) o8[k] = gi[k] * (g[u][k] - db[k] - (xv[u][k] - mu[k]) * is[k] * dg[k]);
-            st8(dx + o[u], o8);
+            for (int u = 0; u < kU; ++u) {
+                if (!ok[u]) continue;
+                if (relu) {
+                    if constexpr (!RECOMPUTE) {
+#pragma unroll
+                        for (int k = 0; k < kVec; ++k) g[u][k] = yv[u][k] > 0.f ? g[u][k] : 0.f;
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < kVec; ++k) g[u][k] = ((xv[u][k] - mu[k]) * ga[k] + be[k]) > 0.f ? g[u][k] : 0.f;
+                    }
+                }
+                if (dres) st8(dres + o[u], g[u]);
+                float o8[kVec];
+#pragma unroll
+                for (int k = 0; k < kVec; ++k) o8[k] = gi[k] * (g[u][k] - db[k] - (xv[u][k] - mu[k]) * is[k] * dg[k]);
+                st8(dx + o[u], o8);
+            }
         }
     }
 }
@@ -552,6 +772,22 @@ int stats_t(const void* x, int64_t rows, int c, float eps, float momentum, float
     return VS_OK;
 }
 
+// which form of the sweeps a launch takes (read at launch time; 0 = the forms without the prefetched first trip)
+bool bn_prefetch() { return vs_option("bn_prefetch") != 0; }
+// The prefetch form of bn_bwd_apply holds the first trip beside the parameters: 170 registers against 128 for bf16, two workgroups
+// per CU instead of four.  It takes the INLINE launches (11.7 -> 8.9 us median in the traced step) whose workgroups are all resident
+// at once either way - the latency-bound deep layers.  The plain apply sweep measured no faster in that form (one hidden round,
+// paid for with the occupancy) and keeps the form without it, as does bn_bwd_partial.
+bool bn_bwd_prefetch(const RowMap& m) {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            cus = 256;
+    }
+    return bn_prefetch() && m.nblocks <= 2 * cus;
+}
+
 }  // namespace
 
 // train-mode BN forward from the conv epilogue's partial rows in ONE launch (nparts small): finalise + normalise
@@ -561,8 +797,10 @@ int launch_bn_apply_from_partials(int dtype, const void* x, const float* partial
     VS_REQUIRE(c % kVec == 0 && c <= 2048, "bn_apply: unsupported channel count %d", c);
     RowMap m = make_rowmap(rows, c);
     const size_t lds = 2 * (size_t)c * sizeof(float);
-    VS_FOR_T(dtype, hipLaunchKernelGGL(bn_apply_inline_kernel<T>, dim3(m.nblocks), dim3(256), lds, s, (const T*)x, partial, nparts, eps,
-                           momentum, mean, invstd, running_mean, running_var, gamma, beta, (const T*)residual, relu, (T*)y, rows, c, m));
+#define VS_APPLY_INLINE(T, PF) hipLaunchKernelGGL((bn_apply_inline_kernel<T, false, PF>), dim3(m.nblocks), dim3(256), lds, s, (const T*)x, partial, nparts, \
+                                                 eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, (const T*)residual, relu, (T*)y, rows, c, m)
+    VS_FOR_T(dtype, { if (bn_prefetch()) VS_APPLY_INLINE(T, true); else VS_APPLY_INLINE(T, false); });
+#undef VS_APPLY_INLINE
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
@@ -573,8 +811,10 @@ int launch_bn_apply_from_bins(int dtype, const void* x, const unsigned long long
     VS_REQUIRE(c % kVec == 0 && c <= 2048 && nb >= 1, "bn_apply: unsupported channel count %d", c);
     RowMap m = make_rowmap(rows, c);
     const size_t lds = 2 * (size_t)c * sizeof(float) + (size_t)std::max(256, 2 * c) * sizeof(long long);
-    VS_FOR_T(dtype, hipLaunchKernelGGL((bn_apply_inline_kernel<T, true>), dim3(m.nblocks), dim3(256), lds, s, (const T*)x, (const float*)bins, nb, eps,
-                           momentum, mean, invstd, running_mean, running_var, gamma, beta, (const T*)residual, relu, (T*)y, rows, c, m, stat_rows));
+#define VS_APPLY_BINS(T, PF) hipLaunchKernelGGL((bn_apply_inline_kernel<T, true, PF>), dim3(m.nblocks), dim3(256), lds, s, (const T*)x, (const float*)bins, nb, \
+                                               eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, (const T*)residual, relu, (T*)y, rows, c, m, stat_rows)
+    VS_FOR_T(dtype, { if (bn_prefetch()) VS_APPLY_BINS(T, true); else VS_APPLY_BINS(T, false); });
+#undef VS_APPLY_BINS
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
@@ -624,28 +864,30 @@ int launch_bn_bwd_from_partials(int dtype, const void* g, const void* x, const f
                                 int nparts, hipStream_t s, const BnSync* sync) {
     VS_REQUIRE(c % kVec == 0 && c <= 2048, "bn_bwd: unsupported channel count %d", c);
     RowMap m = make_rowmap(rows, c);
+    const bool pf = bn_bwd_prefetch(m);
+    // the masked gradient's apply sweep: (dgamma, dbeta) from SG / SB, or (INLINE) summed from the PARTIAL rows inside the sweep
+#define VS_BWD_APPLY_G(T, INLINE, PF, SG, SB, PARTIAL, NPARTS, STAT_ROWS)                                                                  \
+    hipLaunchKernelGGL((bn_bwd_apply<T, false, INLINE, false, PF>), dim3(m.nblocks), dim3(256), 0, s, (const T*)g, (const T*)nullptr, (const T*)x, mean, \
+                       invstd, gamma, (const float*)nullptr, SG, SB, 0, (T*)dx, (T*)dres, rows, c, m, PARTIAL, NPARTS, STAT_ROWS)
     if (sync) {      // finalise locally, sum the two vectors over the ranks, apply with the global sums and row count
         hipLaunchKernelGGL(bn_bwd_finalize, dim3(c), dim3(256), 0, s, partial, nparts, c, dgamma, dbeta);
         VS_LAUNCH_CHECK();
         if (const int rc = bn_sync_sums(*sync, dgamma, dbeta, c, s)) return rc;
-        VS_FOR_T(dtype, hipLaunchKernelGGL((bn_bwd_apply<T, false>), dim3(m.nblocks), dim3(256), 0, s, (const T*)g, (const T*)nullptr,
-                               (const T*)x, mean, invstd, gamma, (const float*)nullptr, sync->scratch + c, sync->scratch, 0, (T*)dx, (T*)dres, rows, c, m,
-                               (const float*)nullptr, 0, rows * sync->world));
+        VS_FOR_T(dtype, VS_BWD_APPLY_G(T, false, false, sync->scratch + c, sync->scratch, (const float*)nullptr, 0, rows * sync->world));
         VS_LAUNCH_CHECK();
         return VS_OK;
     }
     if (nparts <= vs_option("bn_inline_rows") && c <= 512 && 256 % ((2 * c) / 4) == 0) {   // few rows: finalise inside the apply sweep
-        VS_FOR_T(dtype, hipLaunchKernelGGL((bn_bwd_apply<T, false, true>), dim3(m.nblocks), dim3(256), 0, s, (const T*)g, (const T*)nullptr,
-                               (const T*)x, mean, invstd, gamma, (const float*)nullptr, dgamma, dbeta, 0, (T*)dx, (T*)dres, rows, c, m,
-                               partial, nparts));
+        VS_FOR_T(dtype, { if (pf) VS_BWD_APPLY_G(T, true, true, dgamma, dbeta, partial, nparts, 0);
+                          else VS_BWD_APPLY_G(T, true, false, dgamma, dbeta, partial, nparts, 0); });
         VS_LAUNCH_CHECK();
         return VS_OK;
     }
     hipLaunchKernelGGL(bn_bwd_finalize, dim3(c), dim3(256), 0, s, partial, nparts, c, dgamma, dbeta);
     VS_LAUNCH_CHECK();
-    VS_FOR_T(dtype, hipLaunchKernelGGL((bn_bwd_apply<T, false>), dim3(m.nblocks), dim3(256), 0, s, (const T*)g, (const T*)nullptr,
-                           (const T*)x, mean, invstd, gamma, (const float*)nullptr, dgamma, dbeta, 0, (T*)dx, (T*)dres, rows, c, m));
+    VS_FOR_T(dtype, VS_BWD_APPLY_G(T, false, false, dgamma, dbeta, (const float*)nullptr, 0, 0));
     VS_LAUNCH_CHECK();
+#undef VS_BWD_APPLY_G
     return VS_OK;
 }
 

@@ -85,7 +85,10 @@ Opt g_opts[] = {
     {"conv_min_wgs", 512, false}, {"conv_nw8_min_wgs", 128, false}, {"conv_direct_min_px", 262144, false}, {"conv_direct_rows", 32, false},
     {"conv_direct_rows_big", 128, false}, {"conv_ring_max_wgs", 1024, false}, {"conv_stream_min_tiles", 2, false},
     {"wgrad_target", 96, false}, {"wgrad_target_plain", 256, false}, {"wgrad_slab_mb", 16, false}, {"fork_every", 2, false},
-    {"bn_inline_rows", 64, false}, {"nl_max_c", 64, false}};
+    {"bn_inline_rows", 64, false}, {"nl_max_c", 64, false},
+    // forms of the BatchNorm sweeps (norm.hip): 1 = the first trip's row and parameter loads are issued before the statistics prologue,
+    // 0 = the forms without it (same bits: tests/test_hip_bn_prefetch.py)
+    {"bn_prefetch", 1, false}};
 }
 int vs_option(const char* name) {
     for (auto& o : g_opts) {
