@@ -750,6 +750,40 @@ int vs_edt_squared(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, uint32
 int vs_surface_distance_histogram(const uint8_t* from_surface, const uint32_t* d2, int64_t n, int64_t bins, int64_t* hist,
                                   void* stream);
 
+/* ---- connected components and label cleanup (csrc/components.hip) ----
+ * Z x Y x X uint8 label volumes, x fastest, n = Z * Y * X < 2^31 voxels (above: VS_ERR_INVALID, checked from the extents alone).
+ * Two voxels are adjacent under connectivity 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners); an axis of length
+ * 1 has no neighbours (a 1 x H x W volume has 2-D components).  A component is a maximal set of voxels of EQUAL value connected
+ * through adjacent voxels of that value - value 0 included, so every voxel is in exactly one component.  Its id is the linear
+ * index of its lowest-index voxel, its root: the same bits on every run, whatever order the unions happen in.
+ *
+ * vs_label_components: comp[v] = root of v's component (n int32, every one written).  workspace: vs_components_workspace_bytes(Z,
+ * Y, X) bytes of device memory (one int32 per 8 x 8 x 64 tile, at least 4 bytes: never NULL; 0 is returned for extents that
+ * do not fit); its contents need not be initialised.  comp and workspace 4-byte aligned.  Three launches, no host loop. */
+size_t vs_components_workspace_bytes(int64_t Z, int64_t Y, int64_t X);
+int vs_label_components(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int connectivity, int32_t* comp, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* vs_component_sizes: from the comp of vs_label_components (16-byte aligned), size[r] = the voxel count at every root r and 0 at
+ * every other voxel; touches[r] (n bytes, or NULL) = 1 at a root whose component has a voxel with a coordinate equal to 0 or to
+ * extent - 1 on an axis longer than 1, 0 everywhere else.  Both are fully written by the call. */
+int vs_component_sizes(const int32_t* comp, int64_t Z, int64_t Y, int64_t X, int32_t* size, uint8_t* touches, void* stream);
+/* vs_component_largest: key_per_value[c] (256 int64, written by the call) = the largest (size[r] << 32) | (0x7FFFFFFF - r) over
+ * the roots r with labels[r] == c - the largest component of value c, the lower root on a tie - and 0 where c does not occur. */
+int vs_component_largest(const uint8_t* labels, const int32_t* size, int64_t n, int64_t* key_per_value, void* stream);
+/* vs_components_apply: the cleaned volume in one sweep, every decision taken from the labelling of the INPUT.  For a voxel v of
+ * value c whose component has root r:
+ *   c != background: out[v] = background when size[r] < min_size[c], or when keep_root[c] >= 0 and r != keep_root[c]; else c.
+ *   c == background: the component is a hole when hole_max > 0, size[r] <= hole_max, touches[r] == 0 and r > 0; every voxel of a
+ *     hole gets the final value of voxel r - 1, the voxel in front of the root (it exists because the component does not reach
+ *     the boundary, and has another value because it would otherwise be the root): that voxel's own value, or background when
+ *     its component is cleared by the rule above - the hole then stays as it is.  Any other voxel is copied.
+ * min_size and keep_root: 256 device int32 each, indexed by label value (keep_root -1 = keep every component).  counts (4 device
+ * int64, written by the call): components cleared, voxels cleared, holes filled, voxels filled - a hole that stays background is
+ * not counted.  touches may be NULL when hole_max <= 0.  out must NOT overlap labels (VS_ERR_INVALID): a hole reads another
+ * voxel's input value.  comp 16-byte, labels and out 4-byte aligned. */
+int vs_components_apply(const uint8_t* labels, const int32_t* comp, const int32_t* size, const uint8_t* touches, const int32_t* min_size,
+                        const int32_t* keep_root, int background, int64_t hole_max, int64_t n, uint8_t* out, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

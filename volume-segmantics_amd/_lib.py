@@ -244,6 +244,11 @@ _SIGS = {
     "vs_edt_workspace_bytes": (SZ, [I64, I64, I64]),
     "vs_edt_squared": (I, [P, I64, I64, I64, P, P, SZ, P]),
     "vs_surface_distance_histogram": (I, [P, P, I64, I64, P, P]),
+    "vs_components_workspace_bytes": (SZ, [I64, I64, I64]),
+    "vs_label_components": (I, [P, I64, I64, I64, I, P, P, SZ, P]),
+    "vs_component_sizes": (I, [P, I64, I64, I64, P, P, P]),
+    "vs_component_largest": (I, [P, P, I64, P, P]),
+    "vs_components_apply": (I, [P, P, P, P, P, P, I, I64, I64, P, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

@@ -23,8 +23,17 @@ class VolSeg2DPredictionManager(BaseDataManager):
 
     def predict_volume_to_path(self, output_path: Union[Path, None], quality: Union[utils.Quality, None] = None) -> np.ndarray:
         """LOW = one axis, MEDIUM = 3 axes, HIGH = 3 axes x 4 rotations, merged by maximum probability;
-        ``one_hot`` returns per-class vote counts instead (:43-89)."""
+        ``one_hot`` returns per-class vote counts instead (:43-89).  With one of the optional settings keys ``postprocess_min_object_size``,
+        ``postprocess_keep_largest`` or ``postprocess_fill_holes`` set, the merged label volume is cleaned (utilities/components.py, connected
+        components under ``postprocess_connectivity``) before it is saved and returned: ``last_postprocess`` then keeps the raw volume and
+        the report, and ``<stem>_components.json`` / ``.csv`` are written beside the label volume.  The probabilities stay as predicted."""
         one_hot = self.settings.one_hot
+        postprocess = any(getattr(self.settings, key, None) for key in
+                          ("postprocess_min_object_size", "postprocess_keep_largest", "postprocess_fill_holes"))
+        if postprocess and one_hot:
+            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there are no components to clean "
+                             "(unset the postprocess_* keys or set one_hot: False)")
+        self.last_postprocess = None
         axis = utils.get_prediction_axis(self.settings)
         if quality is None:
             quality = utils.get_prediction_quality(self.settings)
@@ -46,9 +55,21 @@ class VolSeg2DPredictionManager(BaseDataManager):
                 prediction, probs = p._predict_12_ways_max_probs(self.data_vol)
         else:
             raise ValueError(f"unknown quality {quality}")
+        report = None
+        if postprocess and prediction is not None:      # every rank that holds the merged volume cleans it: exact integers, so the ranks agree
+            from ...utilities import components
+            if components.postprocess_settings(self.settings)["active"]:
+                raw = prediction
+                prediction, report = components.postprocess_label_volume(raw, self.settings, device=f"cuda:{p.model_device_num}")
+                self.last_postprocess = {"raw": raw, "report": report}
+                logging.info("Components of the merged label volume:\n" + components.component_report_table(report))
         if output_path is not None:
             output_path = Path(output_path)
             utils.save_data_to_hdf5(prediction, output_path, chunking=self.input_data_chunking)
+            if report is not None:
+                from ... import dist as vdist
+                if vdist.world()[0] == 0:
+                    components.write_component_report(output_path.parent / output_path.stem, report)
             if probs is not None and self.settings.output_probs:
                 # the reference hard-codes the name: "<stem>_probs.h5" whatever the label file's suffix (:94-98)
                 utils.save_data_to_hdf5(probs, f"{output_path.parent / output_path.stem}_probs.h5", chunking=self.input_data_chunking)

@@ -1,0 +1,42 @@
+"""model-clean-2d: repair a predicted label volume - drop small connected components, keep the largest component of a class, fill
+small enclosed holes.
+
+    python -m volume_segmantics_amd.scripts.clean_2d_prediction PRED.h5 [--data_dir DIR] [--output OUT.h5]
+
+Reads ``DIR/volseg-settings/2d_model_predict_settings.yaml`` for the keys ``postprocess_min_object_size``, ``postprocess_keep_largest``,
+``postprocess_fill_holes`` and ``postprocess_connectivity`` (utilities/components.py says what each does), cleans the label volume
+``PRED`` - one this engine or the reference wrote - and writes ``<stem of PRED>_cleaned.h5`` under ``DIR`` (or ``OUT``) with
+``<stem of PRED>_components.json`` and ``.csv`` beside it: per label value the components and voxels before, cleared and
+kept, and the holes filled.  Runs the HIP kernels on a GPU and the host route, with the same integers, on a host without one.  With
+no key set the volume is copied and the report says so."""
+from __future__ import annotations
+
+import logging
+
+from ..utilities import arg_parsing
+from ..utilities import config as cfg
+
+
+def main(argv=None) -> None:
+    logging.basicConfig(level=logging.INFO, format=cfg.LOGGING_FMT, datefmt=cfg.LOGGING_DATE_FMT)
+    args = arg_parsing.parse_cleaning_args(argv)
+    root = arg_parsing.root_path(args)
+    pred_path = getattr(args, cfg.PREDICTION_ARG)
+    settings_path = root / cfg.SETTINGS_DIR / cfg.PREDICTION_SETTINGS_FN
+    from types import SimpleNamespace
+    from ..data import get_settings_data
+    from ..utilities import base_data_utils as utils
+    from ..utilities import components
+    settings = get_settings_data(settings_path) if settings_path.is_file() else SimpleNamespace()
+    if not components.postprocess_settings(settings)["active"]:
+        logging.warning(f"no postprocess_* key is set in {settings_path}: the volume is copied as it is")
+    pred, chunking = utils.get_numpy_from_path(pred_path, internal_path=getattr(settings, "data_hdf5_path", "/data"))
+    cleaned, report = components.postprocess_label_volume(pred, settings)
+    logging.info("Components of the label volume:\n" + components.component_report_table(report))
+    out_path = args.output if args.output is not None else root / f"{pred_path.stem}_cleaned.h5"
+    utils.save_data_to_hdf5(cleaned.astype(pred.dtype, copy=False), out_path, chunking=chunking)
+    components.write_component_report(out_path.parent / pred_path.stem, report)
+
+
+if __name__ == "__main__":
+    main()

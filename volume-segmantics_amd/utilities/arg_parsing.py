@@ -1,9 +1,10 @@
-"""Command lines of the commands (scripts/train_2d_model.py, scripts/predict_2d_model.py, scripts/evaluate_2d_model.py); the first two
-take the reference's arguments:
+"""Command lines of the commands (scripts/train_2d_model.py, scripts/predict_2d_model.py, scripts/evaluate_2d_model.py,
+scripts/clean_2d_prediction.py); the first two take the reference's arguments:
 
     train:    --data FILE [FILE ...] --labels FILE [FILE ...] [--data_dir DIR]
     predict:  MODEL FILE [--data_dir DIR]
     evaluate: MODEL FILE --labels LABELS [--data_dir DIR]   |   --prediction PRED --labels LABELS [--data_dir DIR]
+    clean:    PRED [--data_dir DIR] [--output OUT]
 
 ``--data_dir`` (default: the working directory) holds ``volseg-settings/`` and receives every output.  A volume or model file
 with a suffix the engine does not read, or one that does not exist, is a usage error (argparse: exit status 2)."""
@@ -83,6 +84,27 @@ def parse_evaluation_args(argv=None) -> argparse.Namespace:
             parser.error("--prediction scores an existing label volume: give no MODEL or FILE with it")
     elif model is None or data is None:
         parser.error("give MODEL and FILE to predict and score, or --prediction PRED to score an existing label volume")
+    return args
+
+
+def get_2d_cleaning_parser() -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output OUT]: clean an existing label volume with the postprocess_* keys of the predict settings."""
+    parser = argparse.ArgumentParser(description="Clean a predicted label volume: drop small connected components, keep the largest "
+                                                 "component of a class, fill small enclosed holes (postprocess_* settings keys).")
+    parser.add_argument(cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), metavar="PRED",
+                        help="the label volume to clean")
+    parser.add_argument("--output", type=Path, default=None, metavar="OUT",
+                        help="where the cleaned volume goes (default: <stem of PRED>_cleaned.h5 under the data directory)")
+    _add_data_dir(parser)
+    return parser
+
+
+def parse_cleaning_args(argv=None) -> argparse.Namespace:
+    """The clean command's arguments; an --output with a suffix the engine does not write is a usage error (exit 2)."""
+    parser = get_2d_cleaning_parser()
+    args = parser.parse_args(argv)
+    if args.output is not None and args.output.suffix not in cfg.HDF5_SUFFIXES | cfg.NUMPY_SUFFIXES:
+        parser.error(f"--output {args.output} does not end with one of {sorted(cfg.HDF5_SUFFIXES | cfg.NUMPY_SUFFIXES)}")
     return args
 
 
