@@ -784,6 +784,23 @@ int vs_component_largest(const uint8_t* labels, const int32_t* size, int64_t n, 
 int vs_components_apply(const uint8_t* labels, const int32_t* comp, const int32_t* size, const uint8_t* touches, const int32_t* min_size,
                         const int32_t* keep_root, int background, int64_t hole_max, int64_t n, uint8_t* out, int64_t* counts, void* stream);
 
+/* ---- per-component measurements (csrc/measure.hip) ----
+ * vs_component_moments: from a label volume (extents and limits as above) and the comp of vs_label_components, table[r * 20 + f] =
+ * figure f of the component whose root v has row_of_root[v] == r (n int32, one per voxel index: the table row of the component
+ * rooted there; -1 = do not measure; only the entries at roots are read).  Exact int64 figures, the same bits on every run:
+ *    0      voxels
+ *    1 - 3  sum z, sum y, sum x                 4 - 6  sum z^2, sum y^2, sum x^2          7 - 9  sum z y, sum z x, sum y x
+ *   10 - 15 min z, max z, min y, max y, min x, max x
+ *   16 - 18 exposed faces across z, y, x: per voxel, the face neighbours along that axis whose value differs or which lie
+ *           outside the volume; an axis of length 1 has no faces
+ *   19      1 when the component touches the volume's boundary (the definition of vs_component_sizes), else 0
+ * Every sum stays below n * (E - 1)^2, E the longest extent: the caller sees to it that this fits int64.  The table (rows x 20
+ * device int64, 8-byte aligned) is initialised and fully written by the call - a row that no component maps to reads 0 voxels and
+ * an empty box (min = the extent, max = -1); rows == 0 succeeds without a launch.  labels, comp and row_of_root 4-byte aligned.
+ * Two launches (initial values, sweep), no host loop; a volume of one value issues global atomics per wave, not per voxel. */
+int vs_component_moments(const uint8_t* labels, const int32_t* comp, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X, int64_t rows,
+                         int64_t* table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -249,6 +249,7 @@ _SIGS = {
     "vs_component_sizes": (I, [P, I64, I64, I64, P, P, P]),
     "vs_component_largest": (I, [P, P, I64, P, P]),
     "vs_components_apply": (I, [P, P, P, P, P, P, I, I64, I64, P, P, P]),
+    "vs_component_moments": (I, [P, P, P, I64, I64, I64, I64, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

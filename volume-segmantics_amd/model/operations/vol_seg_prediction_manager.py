@@ -26,14 +26,24 @@ class VolSeg2DPredictionManager(BaseDataManager):
         ``one_hot`` returns per-class vote counts instead (:43-89).  With one of the optional settings keys ``postprocess_min_object_size``,
         ``postprocess_keep_largest`` or ``postprocess_fill_holes`` set, the merged label volume is cleaned (utilities/components.py, connected
         components under ``postprocess_connectivity``) before it is saved and returned: ``last_postprocess`` then keeps the raw volume and
-        the report, and ``<stem>_components.json`` / ``.csv`` are written beside the label volume.  The probabilities stay as predicted."""
+        the report, and ``<stem>_components.json`` / ``.csv`` are written beside the label volume.  The probabilities stay as predicted.
+        With ``measure_objects: true`` the volume about to be saved - after any cleanup - is measured (utilities/measurements.py: one row
+        per connected component under ``measure_connectivity``, at least ``measure_min_voxels`` voxels, the background with
+        ``measure_background``, physical units from ``measure_voxel_size``): the summary is logged, ``last_measurements`` keeps the raw
+        integers and the table, and ``<stem>_objects.csv`` / ``.json`` - with ``measure_save_ids`` also ``<stem>_object_ids.h5`` - are
+        written beside the label volume."""
         one_hot = self.settings.one_hot
+        measure = bool(getattr(self.settings, "measure_objects", False))
+        if measure and one_hot:
+            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there are no objects to measure "
+                             "(unset measure_objects or set one_hot: False)")
         postprocess = any(getattr(self.settings, key, None) for key in
                           ("postprocess_min_object_size", "postprocess_keep_largest", "postprocess_fill_holes"))
         if postprocess and one_hot:
             raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there are no components to clean "
                              "(unset the postprocess_* keys or set one_hot: False)")
         self.last_postprocess = None
+        self.last_measurements = None
         axis = utils.get_prediction_axis(self.settings)
         if quality is None:
             quality = utils.get_prediction_quality(self.settings)
@@ -63,9 +73,20 @@ class VolSeg2DPredictionManager(BaseDataManager):
                 prediction, report = components.postprocess_label_volume(raw, self.settings, device=f"cuda:{p.model_device_num}")
                 self.last_postprocess = {"raw": raw, "report": report}
                 logging.info("Components of the merged label volume:\n" + components.component_report_table(report))
+        if measure and prediction is not None:          # the volume that is saved, where it is held: exact integers, so the ranks agree
+            from ...utilities import measurements
+            self.last_measurements = measurements.measure_label_volume(prediction, self.settings, device=f"cuda:{p.model_device_num}")
+            logging.info("Objects of the label volume:\n" + measurements.object_table_text(self.last_measurements["table"]))
         if output_path is not None:
             output_path = Path(output_path)
             utils.save_data_to_hdf5(prediction, output_path, chunking=self.input_data_chunking)
+            if self.last_measurements is not None:
+                from ... import dist as vdist
+                if vdist.world()[0] == 0:
+                    m, stem = self.last_measurements, output_path.parent / output_path.stem
+                    measurements.write_measurements(stem, m["raw"], m["table"], m["settings"])
+                    if m["ids"] is not None:
+                        utils.save_data_to_hdf5(m["ids"], f"{stem}_object_ids.h5", chunking=self.input_data_chunking)
             if report is not None:
                 from ... import dist as vdist
                 if vdist.world()[0] == 0:

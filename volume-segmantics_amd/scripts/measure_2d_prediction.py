@@ -1,0 +1,41 @@
+"""model-measure-2d: measure the objects of a label volume - per connected component its voxels, centroid, bounding box, face-count
+surface, principal axes and whether it touches the boundary.
+
+    python -m volume_segmantics_amd.scripts.measure_2d_prediction PRED.h5 [--data_dir DIR] [--output STEM]
+
+Reads ``DIR/volseg-settings/2d_model_predict_settings.yaml`` for the keys ``measure_connectivity``, ``measure_min_voxels``,
+``measure_background``, ``measure_voxel_size`` and ``measure_save_ids`` (utilities/measurements.py says what each does), measures the
+label volume ``PRED`` - one this engine or the reference wrote - and writes ``<stem of PRED>_objects.csv`` and ``_objects.json`` under
+``DIR`` (or ``STEM_objects.csv`` / ``.json``), with ``measure_save_ids`` also ``_object_ids.h5``.  Runs the HIP kernels on a GPU and the
+host route, with the same integers, on a host without one.  It measures whether or not ``measure_objects`` is set: running the
+command is the request."""
+from __future__ import annotations
+
+import logging
+
+from ..utilities import arg_parsing
+from ..utilities import config as cfg
+
+
+def main(argv=None) -> None:
+    logging.basicConfig(level=logging.INFO, format=cfg.LOGGING_FMT, datefmt=cfg.LOGGING_DATE_FMT)
+    args = arg_parsing.parse_measuring_args(argv)
+    root = arg_parsing.root_path(args)
+    pred_path = getattr(args, cfg.PREDICTION_ARG)
+    settings_path = root / cfg.SETTINGS_DIR / cfg.PREDICTION_SETTINGS_FN
+    from types import SimpleNamespace
+    from ..data import get_settings_data
+    from ..utilities import base_data_utils as utils
+    from ..utilities import measurements
+    settings = get_settings_data(settings_path) if settings_path.is_file() else SimpleNamespace()
+    pred, chunking = utils.get_numpy_from_path(pred_path, internal_path=getattr(settings, "data_hdf5_path", "/data"))
+    m = measurements.measure_label_volume(pred, settings)
+    logging.info("Objects of the label volume:\n" + measurements.object_table_text(m["table"]))
+    stem = args.output if args.output is not None else root / pred_path.stem
+    measurements.write_measurements(stem, m["raw"], m["table"], m["settings"])
+    if m["ids"] is not None:
+        utils.save_data_to_hdf5(m["ids"], f"{stem}_object_ids.h5", chunking=chunking)
+
+
+if __name__ == "__main__":
+    main()
