@@ -801,6 +801,40 @@ int vs_components_apply(const uint8_t* labels, const int32_t* comp, const int32_
 int vs_component_moments(const uint8_t* labels, const int32_t* comp, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X, int64_t rows,
                          int64_t* table, void* stream);
 
+/* ---- surface meshes of a label volume (csrc/mesh.hip) ----
+ * The naive surface net of M = the voxels of a Z x Y x X uint8 label volume (x fastest) whose value is `value`; everything outside
+ * the volume is outside M, on an axis of length 1 too, so the mesh is always closed.  Cell (k, j, i), 0 <= k <= Z, 0 <= j <= Y,
+ * 0 <= i <= X, has the voxel centres (k-1 | k, j-1 | j, i-1 | i) as corners and the linear index (k (Y+1) + j)(X+1) + i;
+ * (Z+1)(Y+1)(X+1) < 2^31 (above: VS_ERR_INVALID, checked from the extents alone).  A cell is active when its 8 corners are neither
+ * all in M nor all outside.  One vertex per active cell, numbered in ascending cell index, at float32(base) + off per axis in
+ * voxel-index coordinates (z, y, x), base = (k-1, j-1, i-1): off = 0.5 under VS_MESH_BLOCKY; under VS_MESH_SMOOTH off_a =
+ * float32(float64(S_a) / float64(2 n)) over the cell's n crossing edges (the two corners differ), S_a the sum of twice the edge
+ * midpoints' offsets along a.  One quad per pair of face-adjacent positions of which exactly one is in M: its owner is the
+ * largest-index cell of the four around that edge; with (a, b, c) the cyclic rotation of (x, y, z) that starts at the edge's axis
+ * and (db, dc) offsets from the owner, its vertices are those of the cells (-1,-1), (0,-1), (0,0), (-1,0) when the lower position
+ * is the one in M and (-1,-1), (-1,0), (0,0), (0,-1) otherwise - counter-clockwise seen from outside M with positions read as
+ * right-handed (x, y, z).  Quads are ordered by owner cell index and, within an owner, by axis z, then y, then x.  Two voxels of M
+ * that touch only along an edge give an edge with 4 quads: it is kept.
+ *
+ * vs_mesh_count: one sweep over the labels and a scan (a memset and up to eight launches, no host loop, no workgroup waits on
+ * another).  totals (4 device int64, written by the call): vertices, then quads across z, y and x - vertices and the quads together
+ * each below 2^31 for the emit pass to be called, which the caller checks.  It leaves in workspace - vs_mesh_workspace_bytes(Z, Y,
+ * X) bytes of device memory, about 0.25 byte per cell plus 8 KiB: never NULL; 0 is returned for extents that do not fit; contents
+ * need not be initialised - what vs_mesh_emit needs: per 64 cells of a row of cells the mask of active cells and the exclusive
+ * vertex and quad offsets.
+ * workspace and totals 8-byte aligned; labels need no alignment.  A value that does not occur gives totals of 0.
+ *
+ * vs_mesh_emit: from the same labels, extents and value and the workspace vs_mesh_count left, vertices (totals[0] x 3 float32, (z,
+ * y, x)) and quads ((totals[1] + totals[2] + totals[3]) x 4 int32 vertex ids): every element is written, nothing else is touched,
+ * no atomics - the same bits on every run.  vertices 4-byte, quads 16-byte aligned.  With totals of 0 pass NULL for both: the call
+ * succeeds without a launch.  One launch. */
+enum { VS_MESH_SMOOTH = 0, VS_MESH_BLOCKY = 1 };
+size_t vs_mesh_workspace_bytes(int64_t Z, int64_t Y, int64_t X);
+int vs_mesh_count(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, void* workspace, size_t workspace_bytes,
+                  int64_t* totals, void* stream);
+int vs_mesh_emit(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int style, const void* workspace,
+                 size_t workspace_bytes, float* vertices, int32_t* quads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

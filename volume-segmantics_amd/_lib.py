@@ -250,6 +250,9 @@ _SIGS = {
     "vs_component_largest": (I, [P, P, I64, P, P]),
     "vs_components_apply": (I, [P, P, P, P, P, P, I, I64, I64, P, P, P]),
     "vs_component_moments": (I, [P, P, P, I64, I64, I64, I64, P, P]),
+    "vs_mesh_workspace_bytes": (SZ, [I64, I64, I64]),
+    "vs_mesh_count": (I, [P, I64, I64, I64, I, P, SZ, P, P]),
+    "vs_mesh_emit": (I, [P, I64, I64, I64, I, I, P, SZ, P, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

@@ -31,8 +31,16 @@ class VolSeg2DPredictionManager(BaseDataManager):
         per connected component under ``measure_connectivity``, at least ``measure_min_voxels`` voxels, the background with
         ``measure_background``, physical units from ``measure_voxel_size``): the summary is logged, ``last_measurements`` keeps the raw
         integers and the table, and ``<stem>_objects.csv`` / ``.json`` - with ``measure_save_ids`` also ``<stem>_object_ids.h5`` - are
-        written beside the label volume."""
+        written beside the label volume.
+        With ``mesh_surfaces: true`` the same volume is meshed (utilities/meshes.py: per value of ``mesh_values`` a closed surface net in
+        ``mesh_style``, physical units from ``mesh_voxel_size``): the summary is logged, ``last_meshes`` keeps the arrays and the figures,
+        and ``<stem>_mesh_<value>.ply`` / ``.stl`` (``mesh_format``, ``mesh_triangulate``) and ``<stem>_meshes.json`` are written beside the
+        label volume."""
         one_hot = self.settings.one_hot
+        mesh = bool(getattr(self.settings, "mesh_surfaces", False))
+        if mesh and one_hot:
+            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there is no surface to mesh "
+                             "(unset mesh_surfaces or set one_hot: False)")
         measure = bool(getattr(self.settings, "measure_objects", False))
         if measure and one_hot:
             raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there are no objects to measure "
@@ -44,6 +52,7 @@ class VolSeg2DPredictionManager(BaseDataManager):
                              "(unset the postprocess_* keys or set one_hot: False)")
         self.last_postprocess = None
         self.last_measurements = None
+        self.last_meshes = None
         axis = utils.get_prediction_axis(self.settings)
         if quality is None:
             quality = utils.get_prediction_quality(self.settings)
@@ -77,9 +86,17 @@ class VolSeg2DPredictionManager(BaseDataManager):
             from ...utilities import measurements
             self.last_measurements = measurements.measure_label_volume(prediction, self.settings, device=f"cuda:{p.model_device_num}")
             logging.info("Objects of the label volume:\n" + measurements.object_table_text(self.last_measurements["table"]))
+        if mesh and prediction is not None:             # the volume that is saved: the order of vertices and quads is fixed, so the ranks agree
+            from ...utilities import meshes
+            self.last_meshes = meshes.mesh_label_volume(prediction, self.settings, device=f"cuda:{p.model_device_num}")
+            logging.info("Surface meshes of the label volume:\n" + meshes.mesh_summary_text(self.last_meshes["summary"]))
         if output_path is not None:
             output_path = Path(output_path)
             utils.save_data_to_hdf5(prediction, output_path, chunking=self.input_data_chunking)
+            if self.last_meshes is not None:
+                from ... import dist as vdist
+                if vdist.world()[0] == 0:
+                    meshes.write_meshes(output_path.parent / output_path.stem, self.last_meshes)
             if self.last_measurements is not None:
                 from ... import dist as vdist
                 if vdist.world()[0] == 0:

@@ -1,11 +1,13 @@
 """Command lines of the commands (scripts/train_2d_model.py, scripts/predict_2d_model.py, scripts/evaluate_2d_model.py,
-scripts/clean_2d_prediction.py, scripts/measure_2d_prediction.py); the first two take the reference's arguments:
+scripts/clean_2d_prediction.py, scripts/measure_2d_prediction.py, scripts/mesh_2d_prediction.py); the first two take the reference's
+arguments:
 
     train:    --data FILE [FILE ...] --labels FILE [FILE ...] [--data_dir DIR]
     predict:  MODEL FILE [--data_dir DIR]
     evaluate: MODEL FILE --labels LABELS [--data_dir DIR]   |   --prediction PRED --labels LABELS [--data_dir DIR]
     clean:    PRED [--data_dir DIR] [--output OUT]
     measure:  PRED [--data_dir DIR] [--output STEM]
+    mesh:     PRED [--data_dir DIR] [--output STEM]
 
 ``--data_dir`` (default: the working directory) holds ``volseg-settings/`` and receives every output.  A volume or model file
 with a suffix the engine does not read, or one that does not exist, is a usage error (argparse: exit status 2)."""
@@ -124,6 +126,27 @@ def get_2d_measuring_parser() -> argparse.ArgumentParser:
 def parse_measuring_args(argv=None) -> argparse.Namespace:
     """The measure command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
     parser = get_2d_measuring_parser()
+    args = parser.parse_args(argv)
+    if args.output is not None and not args.output.resolve().parent.is_dir():
+        parser.error(f"--output {args.output}: the directory {args.output.resolve().parent} does not exist")
+    return args
+
+
+def get_2d_meshing_parser() -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output STEM]: mesh the surfaces of an existing label volume with the mesh_* keys of the predict settings."""
+    parser = argparse.ArgumentParser(description="Export surface meshes of a label volume: per label value a closed surface net as binary "
+                                                 "PLY or STL (mesh_* settings keys).")
+    parser.add_argument(cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), metavar="PRED",
+                        help="the label volume to mesh")
+    parser.add_argument("--output", type=Path, default=None, metavar="STEM",
+                        help="the files written are STEM_mesh_<value>.ply / .stl and STEM_meshes.json (default: <stem of PRED> under the data directory)")
+    _add_data_dir(parser)
+    return parser
+
+
+def parse_meshing_args(argv=None) -> argparse.Namespace:
+    """The mesh command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
+    parser = get_2d_meshing_parser()
     args = parser.parse_args(argv)
     if args.output is not None and not args.output.resolve().parent.is_dir():
         parser.error(f"--output {args.output}: the directory {args.output.resolve().parent} does not exist")
