@@ -95,8 +95,8 @@ def main():
     ok = True
     for name, labels, connectivity, min_voxels, background in cases:
         flat = labels.reshape(-1)
-        comp = co._label_device(flat, shape, connectivity)
-        size, touches = co._sizes_device(comp, shape)
+        comp = co.label_device(flat, shape, connectivity)
+        size, touches = co.sizes_device(comp, shape)
         roots = torch.nonzero(size).reshape(-1)
         keep = size[roots] >= min_voxels
         if not background:

@@ -191,6 +191,28 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline size_t dtype_size(int dt) { return dt == VS_F32 ? 4 : 2; }
 
+// compute units of the device that is current at the first call; 256 when the query fails
+inline int device_cus() {
+    static int cached = 0;
+    if (!cached) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            cus = 256;
+        cached = cus;
+    }
+    return cached;
+}
+// the grid of a persistent sweep: 8 workgroups of 4 waves per CU, 8 waves per SIMD
+inline int persistent_workgroups() { return device_cus() * 8; }
+
+// a label volume's extents: each at least 1, and the Z x Y x X voxels (pad 0) or the (Z+1)(Y+1)(X+1) cells (pad 1) below 2^31
+inline bool extents_fit(int64_t Z, int64_t Y, int64_t X, int pad) {
+    constexpr int64_t limit = 1LL << 31;
+    if (Z < 1 || Y < 1 || X < 1 || Z >= limit || Y >= limit || X >= limit) return false;
+    if ((Z + pad) * (Y + pad) >= limit) return false;
+    return (Z + pad) * (Y + pad) * (X + pad) < limit;
+}
+
 // One launcher body per storage type.  VS_F16 is the inference precision: the operators of an evaluation-mode forward pass
 // dispatch through VS_FOR_T; the training-only operators keep their two-way dispatch behind VS_NO_F16.
 #define VS_FOR_T(dtype, ...)                                          \

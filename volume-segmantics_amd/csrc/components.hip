@@ -44,28 +44,11 @@ constexpr int kThreads = 256, kWaves = kThreads / 64;
 constexpr int kSpanSteps = 32;                 // vs_component_sizes: steps of 256 voxels a wave takes over its contiguous span
 constexpr int64_t kLimit = 1LL << 31;
 
-bool extents_fit(int64_t Z, int64_t Y, int64_t X) {
-    if (Z < 1 || Y < 1 || X < 1 || Z >= kLimit || Y >= kLimit || X >= kLimit) return false;
-    if (Z * Y >= kLimit) return false;
-    return Z * Y * X < kLimit;
-}
-
 struct Grid {                                  // the volume and its tiling
     int Z, Y, X, nz, ny, nx;
 };
 Grid make_grid(int64_t Z, int64_t Y, int64_t X) {
     return Grid{(int)Z, (int)Y, (int)X, (int)((Z + kTZ - 1) / kTZ), (int)((Y + kTY - 1) / kTY), (int)((X + kTX - 1) / kTX)};
-}
-
-int persistent_workgroups() {
-    static int cached = 0;
-    if (!cached) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        cached = cus * 8;
-    }
-    return cached;
 }
 
 // ---- union-find --------------------------------------------------------------------------------------------------------------
@@ -405,11 +388,11 @@ int64_t sweep_grid(int64_t n) {
 }  // namespace
 
 #define VS_COMPONENT_EXTENTS(what)                                                                                                         \
-    VS_REQUIRE(extents_fit(Z, Y, X), what ": extents %lld x %lld x %lld - every extent must be at least 1 and the volume below 2^31 voxels " \
+    VS_REQUIRE(extents_fit(Z, Y, X, 0), what ": extents %lld x %lld x %lld - every extent must be at least 1 and the volume below 2^31 voxels " \
                "(component ids are int32 voxel indices)", (long long)Z, (long long)Y, (long long)X)
 
 extern "C" size_t vs_components_workspace_bytes(int64_t Z, int64_t Y, int64_t X) {
-    if (!extents_fit(Z, Y, X)) return 0;
+    if (!extents_fit(Z, Y, X, 0)) return 0;
     const Grid g = make_grid(Z, Y, X);
     return (size_t)g.nz * g.ny * g.nx * sizeof(int);
 }

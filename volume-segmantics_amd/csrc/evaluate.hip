@@ -146,17 +146,6 @@ __global__ __launch_bounds__(kThreads) void confusion_kernel(const uint8_t* __re
     }
 }
 
-int persistent_workgroups() {
-    static int cached = 0;
-    if (!cached) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        cached = cus * 8;                        // 8 workgroups of 4 waves per CU: 8 waves per SIMD, 4.2 KB of LDS each
-    }
-    return cached;
-}
-
 }  // namespace
 
 extern "C" int vs_confusion_matrix(const uint8_t* truth, const uint8_t* pred, int64_t n, int classes, const uint8_t* truth_lut,

@@ -43,13 +43,6 @@ constexpr int kSpanSteps = 32;                 // steps of 256 voxels a wave tak
 constexpr int kSlots = 32;                     // rows a wave's cache holds
 constexpr int kRounds = 8;                     // rows per sub-step a wave groups by ballot
 constexpr int kFields = 20;                    // utilities/measurements.py FIELDS
-constexpr int64_t kLimit = 1LL << 31;
-
-bool extents_fit(int64_t Z, int64_t Y, int64_t X) {
-    if (Z < 1 || Y < 1 || X < 1 || Z >= kLimit || Y >= kLimit || X >= kLimit) return false;
-    if (Z * Y >= kLimit) return false;
-    return Z * Y * X < kLimit;
-}
 
 // fields 10, 12, 14 are minima, 11, 13, 15 and 19 maxima (19: 0 / 1), the others sums
 __device__ __forceinline__ bool is_min(int f) { return f == 10 || f == 12 || f == 14; }
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const uint8_t* __rest
 
 extern "C" int vs_component_moments(const uint8_t* labels, const int32_t* comp, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X,
                                     int64_t rows, int64_t* table, void* stream) {
-    VS_REQUIRE(extents_fit(Z, Y, X), "component_moments: extents %lld x %lld x %lld - every extent must be at least 1 and the volume below 2^31 "
+    VS_REQUIRE(extents_fit(Z, Y, X, 0), "component_moments: extents %lld x %lld x %lld - every extent must be at least 1 and the volume below 2^31 "
                "voxels (component ids are int32 voxel indices)", (long long)Z, (long long)Y, (long long)X);
     const int64_t n = Z * Y * X;
     VS_REQUIRE(rows >= 0 && rows <= n, "component_moments: %lld rows - a volume of %lld voxels has between 0 and that many components",

@@ -37,15 +37,8 @@ constexpr int kRowsPerWave = 8;                // rows of cells (k, j0 .. j0 + 7
 constexpr int kSlots = kRowsPerWave + 1;       // the voxel rows y = j0 - 1 .. j0 + 7 those share, per z
 constexpr int kScanItems = 4;                  // words a thread of the scan holds
 constexpr int kScanTile = kThreads * kScanItems;       // words one workgroup reduces or scans: 1024; three levels reach 2^30 chunks
-constexpr int64_t kLimit = 1LL << 31;
 constexpr uint64_t kVertexField = 0x7FFFFFFFull;       // packed word: vertices in bits 0 .. 30, quads from bit 31
 constexpr int kTotalSlots = 256;               // partial totals the count sweep's workgroups spread their atomics over
-
-bool extents_fit(int64_t Z, int64_t Y, int64_t X) {
-    if (Z < 1 || Y < 1 || X < 1 || Z >= kLimit || Y >= kLimit || X >= kLimit) return false;
-    if ((Z + 1) * (Y + 1) >= kLimit) return false;
-    return (Z + 1) * (Y + 1) * (X + 1) < kLimit;
-}
 
 struct Layout {                                // the workspace: masks, packed counts / offsets, the two upper scan levels, the partial totals
     int64_t chunks_per_row, chunks, n1, n2;
@@ -352,7 +345,7 @@ __global__ __launch_bounds__(kThreads) void mesh_emit_kernel(const uint8_t* __re
 }
 
 int check_common(const char* who, int64_t Z, int64_t Y, int64_t X, int value, size_t workspace_bytes, Layout* l) {
-    VS_REQUIRE(extents_fit(Z, Y, X), "%s: extents %lld x %lld x %lld - every extent must be at least 1 and the (Z+1)(Y+1)(X+1) cells below 2^31 "
+    VS_REQUIRE(extents_fit(Z, Y, X, 1), "%s: extents %lld x %lld x %lld - every extent must be at least 1 and the (Z+1)(Y+1)(X+1) cells below 2^31 "
                "(vertex ids are int32)", who, (long long)Z, (long long)Y, (long long)X);
     VS_REQUIRE(value >= 0 && value <= 255, "%s: value %d is not a uint8 value", who, value);
     *l = layout_of(Z, Y, X);
@@ -365,7 +358,7 @@ unsigned sweep_groups(const Layout& l) { return (unsigned)((l.columns + kWaves -
 }  // namespace
 
 extern "C" size_t vs_mesh_workspace_bytes(int64_t Z, int64_t Y, int64_t X) {
-    return extents_fit(Z, Y, X) ? layout_of(Z, Y, X).bytes : 0;
+    return extents_fit(Z, Y, X, 1) ? layout_of(Z, Y, X).bytes : 0;
 }
 
 extern "C" int vs_mesh_count(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, void* workspace, size_t workspace_bytes,

@@ -778,15 +778,7 @@ bool bn_prefetch() { return vs_option("bn_prefetch") != 0; }
 // per CU instead of four.  It takes the INLINE launches (11.7 -> 8.9 us median in the traced step) whose workgroups are all resident
 // at once either way - the latency-bound deep layers.  The plain apply sweep measured no faster in that form (one hidden round,
 // paid for with the occupancy) and keeps the form without it, as does bn_bwd_partial.
-bool bn_bwd_prefetch(const RowMap& m) {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-    }
-    return bn_prefetch() && m.nblocks <= 2 * cus;
-}
+bool bn_bwd_prefetch(const RowMap& m) { return bn_prefetch() && m.nblocks <= 2 * device_cus(); }
 
 }  // namespace
 

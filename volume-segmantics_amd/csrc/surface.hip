@@ -38,17 +38,6 @@ constexpr int kMaxLdsAxis = 512;               // longest axis a tile holds: 512
 constexpr int kSmallBins = 1024;               // bins of the workgroup's LDS histogram
 constexpr int kRegBins = 3;                    // bins counted in registers
 
-int persistent_workgroups() {
-    static int cached = 0;
-    if (!cached) {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-            cus = 256;
-        cached = cus * 8;
-    }
-    return cached;
-}
-
 // (Z-1)^2 + (Y-1)^2 + (X-1)^2 < 2^32 - 1: every squared distance in the volume is a uint32 below the "no seed" mark
 bool extents_fit(int64_t Z, int64_t Y, int64_t X) {
     if (Z < 1 || Y < 1 || X < 1 || Z > 65536 || Y > 65536 || X > 65536) return false;

@@ -3,13 +3,57 @@
 import logging
 from pathlib import Path
 from types import SimpleNamespace
-from typing import Union
+from typing import Callable, NamedTuple, Union
 
 import numpy as np
 
 from ...data.base_data_manager import BaseDataManager
 from ...utilities import base_data_utils as utils
+from ...utilities import components, measurements, meshes
 from .vol_seg_2d_predictor import VolSeg2dPredictor
+
+
+class LabelStep(NamedTuple):
+    """One optional step on the merged label volume.  The functions of the utilities modules are looked up when a step runs."""
+    name: str
+    asked: Callable       # settings -> whether the settings ask for the step
+    refusal: str          # why ``one_hot: True`` cannot have it, and what to unset
+    run: Callable         # (volume, settings, device) -> (the volume to go on with, what to remember), or None: nothing to do after all
+    log: Callable         # what is remembered -> the text for the log
+    remember: str         # the manager's attribute that keeps it
+    write: Callable       # (stem, what is remembered, save(array, path)) -> the files beside the label volume
+
+
+def _clean(volume, settings, device):
+    if not components.postprocess_settings(settings)["active"]:
+        return None
+    cleaned, report = components.postprocess_label_volume(volume, settings, device=device)
+    return cleaned, {"raw": volume, "report": report}
+
+
+def _write_measurements(stem, m, save):
+    measurements.write_measurements(stem, m["raw"], m["table"], m["settings"])
+    if m["ids"] is not None:
+        save(m["ids"], f"{stem}_object_ids.h5")
+
+
+# in the order they run: the measurements and the meshes are those of the volume that is saved, after any cleanup
+LABEL_STEPS = (
+    LabelStep("clean", lambda s: any(getattr(s, key, None) for key in ("postprocess_min_object_size", "postprocess_keep_largest", "postprocess_fill_holes")),
+              "there are no components to clean (unset the postprocess_* keys or set one_hot: False)", _clean,
+              lambda kept: "Components of the merged label volume:\n" + components.component_report_table(kept["report"]),
+              "last_postprocess", lambda stem, kept, save: components.write_component_report(stem, kept["report"])),
+    LabelStep("measure", lambda s: bool(getattr(s, "measure_objects", False)),
+              "there are no objects to measure (unset measure_objects or set one_hot: False)",
+              lambda volume, s, device: (volume, measurements.measure_label_volume(volume, s, device=device)),
+              lambda m: "Objects of the label volume:\n" + measurements.object_table_text(m["table"]),
+              "last_measurements", _write_measurements),
+    LabelStep("mesh", lambda s: bool(getattr(s, "mesh_surfaces", False)),
+              "there is no surface to mesh (unset mesh_surfaces or set one_hot: False)",
+              lambda volume, s, device: (volume, meshes.mesh_label_volume(volume, s, device=device)),
+              lambda m: "Surface meshes of the label volume:\n" + meshes.mesh_summary_text(m["summary"]),
+              "last_meshes", lambda stem, m, save: meshes.write_meshes(stem, m)),
+)
 
 
 class VolSeg2DPredictionManager(BaseDataManager):
@@ -37,22 +81,11 @@ class VolSeg2DPredictionManager(BaseDataManager):
         and ``<stem>_mesh_<value>.ply`` / ``.stl`` (``mesh_format``, ``mesh_triangulate``) and ``<stem>_meshes.json`` are written beside the
         label volume."""
         one_hot = self.settings.one_hot
-        mesh = bool(getattr(self.settings, "mesh_surfaces", False))
-        if mesh and one_hot:
-            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there is no surface to mesh "
-                             "(unset mesh_surfaces or set one_hot: False)")
-        measure = bool(getattr(self.settings, "measure_objects", False))
-        if measure and one_hot:
-            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there are no objects to measure "
-                             "(unset measure_objects or set one_hot: False)")
-        postprocess = any(getattr(self.settings, key, None) for key in
-                          ("postprocess_min_object_size", "postprocess_keep_largest", "postprocess_fill_holes"))
-        if postprocess and one_hot:
-            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: there are no components to clean "
-                             "(unset the postprocess_* keys or set one_hot: False)")
-        self.last_postprocess = None
-        self.last_measurements = None
-        self.last_meshes = None
+        steps = [step for step in LABEL_STEPS if step.asked(self.settings)]
+        if one_hot and steps:
+            raise ValueError("one_hot: True predicts per-class vote counts, not a label volume: " + steps[0].refusal)
+        for step in LABEL_STEPS:
+            setattr(self, step.remember, None)
         axis = utils.get_prediction_axis(self.settings)
         if quality is None:
             quality = utils.get_prediction_quality(self.settings)
@@ -74,43 +107,28 @@ class VolSeg2DPredictionManager(BaseDataManager):
                 prediction, probs = p._predict_12_ways_max_probs(self.data_vol)
         else:
             raise ValueError(f"unknown quality {quality}")
-        report = None
-        if postprocess and prediction is not None:      # every rank that holds the merged volume cleans it: exact integers, so the ranks agree
-            from ...utilities import components
-            if components.postprocess_settings(self.settings)["active"]:
-                raw = prediction
-                prediction, report = components.postprocess_label_volume(raw, self.settings, device=f"cuda:{p.model_device_num}")
-                self.last_postprocess = {"raw": raw, "report": report}
-                logging.info("Components of the merged label volume:\n" + components.component_report_table(report))
-        if measure and prediction is not None:          # the volume that is saved, where it is held: exact integers, so the ranks agree
-            from ...utilities import measurements
-            self.last_measurements = measurements.measure_label_volume(prediction, self.settings, device=f"cuda:{p.model_device_num}")
-            logging.info("Objects of the label volume:\n" + measurements.object_table_text(self.last_measurements["table"]))
-        if mesh and prediction is not None:             # the volume that is saved: the order of vertices and quads is fixed, so the ranks agree
-            from ...utilities import meshes
-            self.last_meshes = meshes.mesh_label_volume(prediction, self.settings, device=f"cuda:{p.model_device_num}")
-            logging.info("Surface meshes of the label volume:\n" + meshes.mesh_summary_text(self.last_meshes["summary"]))
+        done = []
+        for step in steps:
+            # every rank that holds the merged volume works on it: exact integers and a fixed order of vertices and quads, so the ranks agree
+            result = step.run(prediction, self.settings, f"cuda:{p.model_device_num}") if prediction is not None else None
+            if result is not None:
+                prediction, kept = result
+                setattr(self, step.remember, kept)
+                logging.info(step.log(kept))
+                done.append((step, kept))
         if output_path is not None:
             output_path = Path(output_path)
-            utils.save_data_to_hdf5(prediction, output_path, chunking=self.input_data_chunking)
-            if self.last_meshes is not None:
+            stem = output_path.parent / output_path.stem
+            save = lambda data, path: utils.save_data_to_hdf5(data, path, chunking=self.input_data_chunking)      # noqa: E731
+            save(prediction, output_path)
+            if done:
                 from ... import dist as vdist
                 if vdist.world()[0] == 0:
-                    meshes.write_meshes(output_path.parent / output_path.stem, self.last_meshes)
-            if self.last_measurements is not None:
-                from ... import dist as vdist
-                if vdist.world()[0] == 0:
-                    m, stem = self.last_measurements, output_path.parent / output_path.stem
-                    measurements.write_measurements(stem, m["raw"], m["table"], m["settings"])
-                    if m["ids"] is not None:
-                        utils.save_data_to_hdf5(m["ids"], f"{stem}_object_ids.h5", chunking=self.input_data_chunking)
-            if report is not None:
-                from ... import dist as vdist
-                if vdist.world()[0] == 0:
-                    components.write_component_report(output_path.parent / output_path.stem, report)
+                    for step, kept in done:
+                        step.write(stem, kept, save)
             if probs is not None and self.settings.output_probs:
                 # the reference hard-codes the name: "<stem>_probs.h5" whatever the label file's suffix (:94-98)
-                utils.save_data_to_hdf5(probs, f"{output_path.parent / output_path.stem}_probs.h5", chunking=self.input_data_chunking)
+                save(probs, f"{stem}_probs.h5")
         return prediction
 
     def evaluate_volume(self, label_vol: Union[Path, str, np.ndarray], output_path: Union[Path, None] = None,

@@ -14,28 +14,19 @@ from __future__ import annotations
 import logging
 
 from ..utilities import arg_parsing
-from ..utilities import config as cfg
 
 
 def main(argv=None) -> None:
-    logging.basicConfig(level=logging.INFO, format=cfg.LOGGING_FMT, datefmt=cfg.LOGGING_DATE_FMT)
-    args = arg_parsing.parse_cleaning_args(argv)
-    root = arg_parsing.root_path(args)
-    pred_path = getattr(args, cfg.PREDICTION_ARG)
-    settings_path = root / cfg.SETTINGS_DIR / cfg.PREDICTION_SETTINGS_FN
-    from types import SimpleNamespace
-    from ..data import get_settings_data
+    a = arg_parsing.open_label_volume(arg_parsing.parse_cleaning_args, argv)
     from ..utilities import base_data_utils as utils
     from ..utilities import components
-    settings = get_settings_data(settings_path) if settings_path.is_file() else SimpleNamespace()
-    if not components.postprocess_settings(settings)["active"]:
-        logging.warning(f"no postprocess_* key is set in {settings_path}: the volume is copied as it is")
-    pred, chunking = utils.get_numpy_from_path(pred_path, internal_path=getattr(settings, "data_hdf5_path", "/data"))
-    cleaned, report = components.postprocess_label_volume(pred, settings)
+    if not components.postprocess_settings(a.settings)["active"]:
+        logging.warning(f"no postprocess_* key is set in {a.settings_path}: the volume is copied as it is")
+    cleaned, report = components.postprocess_label_volume(a.pred, a.settings)
     logging.info("Components of the label volume:\n" + components.component_report_table(report))
-    out_path = args.output if args.output is not None else root / f"{pred_path.stem}_cleaned.h5"
-    utils.save_data_to_hdf5(cleaned.astype(pred.dtype, copy=False), out_path, chunking=chunking)
-    components.write_component_report(out_path.parent / pred_path.stem, report)
+    out_path = a.output if a.output is not None else a.stem.parent / f"{a.pred_path.stem}_cleaned.h5"
+    utils.save_data_to_hdf5(cleaned.astype(a.pred.dtype, copy=False), out_path, chunking=a.chunking)
+    components.write_component_report(out_path.parent / a.pred_path.stem, report)
 
 
 if __name__ == "__main__":

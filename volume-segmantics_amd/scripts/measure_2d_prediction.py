@@ -14,27 +14,18 @@ from __future__ import annotations
 import logging
 
 from ..utilities import arg_parsing
-from ..utilities import config as cfg
 
 
 def main(argv=None) -> None:
-    logging.basicConfig(level=logging.INFO, format=cfg.LOGGING_FMT, datefmt=cfg.LOGGING_DATE_FMT)
-    args = arg_parsing.parse_measuring_args(argv)
-    root = arg_parsing.root_path(args)
-    pred_path = getattr(args, cfg.PREDICTION_ARG)
-    settings_path = root / cfg.SETTINGS_DIR / cfg.PREDICTION_SETTINGS_FN
-    from types import SimpleNamespace
-    from ..data import get_settings_data
+    a = arg_parsing.open_label_volume(arg_parsing.parse_measuring_args, argv)
     from ..utilities import base_data_utils as utils
     from ..utilities import measurements
-    settings = get_settings_data(settings_path) if settings_path.is_file() else SimpleNamespace()
-    pred, chunking = utils.get_numpy_from_path(pred_path, internal_path=getattr(settings, "data_hdf5_path", "/data"))
-    m = measurements.measure_label_volume(pred, settings)
+    m = measurements.measure_label_volume(a.pred, a.settings)
     logging.info("Objects of the label volume:\n" + measurements.object_table_text(m["table"]))
-    stem = args.output if args.output is not None else root / pred_path.stem
+    stem = a.output if a.output is not None else a.stem
     measurements.write_measurements(stem, m["raw"], m["table"], m["settings"])
     if m["ids"] is not None:
-        utils.save_data_to_hdf5(m["ids"], f"{stem}_object_ids.h5", chunking=chunking)
+        utils.save_data_to_hdf5(m["ids"], f"{stem}_object_ids.h5", chunking=a.chunking)
 
 
 if __name__ == "__main__":

@@ -12,25 +12,14 @@ from __future__ import annotations
 import logging
 
 from ..utilities import arg_parsing
-from ..utilities import config as cfg
 
 
 def main(argv=None) -> None:
-    logging.basicConfig(level=logging.INFO, format=cfg.LOGGING_FMT, datefmt=cfg.LOGGING_DATE_FMT)
-    args = arg_parsing.parse_meshing_args(argv)
-    root = arg_parsing.root_path(args)
-    pred_path = getattr(args, cfg.PREDICTION_ARG)
-    settings_path = root / cfg.SETTINGS_DIR / cfg.PREDICTION_SETTINGS_FN
-    from types import SimpleNamespace
-    from ..data import get_settings_data
-    from ..utilities import base_data_utils as utils
+    a = arg_parsing.open_label_volume(arg_parsing.parse_meshing_args, argv)
     from ..utilities import meshes
-    settings = get_settings_data(settings_path) if settings_path.is_file() else SimpleNamespace()
-    pred, _ = utils.get_numpy_from_path(pred_path, internal_path=getattr(settings, "data_hdf5_path", "/data"))
-    m = meshes.mesh_label_volume(pred, settings)
+    m = meshes.mesh_label_volume(a.pred, a.settings)
     logging.info("Surface meshes of the label volume:\n" + meshes.mesh_summary_text(m["summary"]))
-    stem = args.output if args.output is not None else root / pred_path.stem
-    meshes.write_meshes(stem, m)
+    meshes.write_meshes(a.output if a.output is not None else a.stem, m)
 
 
 if __name__ == "__main__":

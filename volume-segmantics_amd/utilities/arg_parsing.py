@@ -90,16 +90,37 @@ def parse_evaluation_args(argv=None) -> argparse.Namespace:
     return args
 
 
-def get_2d_cleaning_parser() -> argparse.ArgumentParser:
-    """PRED [--data_dir DIR] [--output OUT]: clean an existing label volume with the postprocess_* keys of the predict settings."""
-    parser = argparse.ArgumentParser(description="Clean a predicted label volume: drop small connected components, keep the largest "
-                                                 "component of a class, fill small enclosed holes (postprocess_* settings keys).")
-    parser.add_argument(cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), metavar="PRED",
-                        help="the label volume to clean")
-    parser.add_argument("--output", type=Path, default=None, metavar="OUT",
-                        help="where the cleaned volume goes (default: <stem of PRED>_cleaned.h5 under the data directory)")
+def _label_volume_parser(description: str, pred_help: str, metavar: str, output_help: str) -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output OUT | STEM]: the command line of the commands that work on an existing label volume"""
+    parser = argparse.ArgumentParser(description=description)
+    parser.add_argument(cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), metavar="PRED", help=pred_help)
+    parser.add_argument("--output", type=Path, default=None, metavar=metavar, help=output_help)
     _add_data_dir(parser)
     return parser
+
+
+def get_2d_cleaning_parser() -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output OUT]: clean an existing label volume with the postprocess_* keys of the predict settings."""
+    return _label_volume_parser("Clean a predicted label volume: drop small connected components, keep the largest "
+                                "component of a class, fill small enclosed holes (postprocess_* settings keys).",
+                                "the label volume to clean", "OUT",
+                                "where the cleaned volume goes (default: <stem of PRED>_cleaned.h5 under the data directory)")
+
+
+def get_2d_measuring_parser() -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output STEM]: measure the objects of an existing label volume with the measure_* keys of the predict settings."""
+    return _label_volume_parser("Measure the objects of a label volume: per connected component its voxels, centroid, "
+                                "bounding box, surface, principal axes (measure_* settings keys).",
+                                "the label volume to measure", "STEM",
+                                "the files written are STEM_objects.csv and STEM_objects.json (default: <stem of PRED> under the data directory)")
+
+
+def get_2d_meshing_parser() -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output STEM]: mesh the surfaces of an existing label volume with the mesh_* keys of the predict settings."""
+    return _label_volume_parser("Export surface meshes of a label volume: per label value a closed surface net as binary "
+                                "PLY or STL (mesh_* settings keys).",
+                                "the label volume to mesh", "STEM",
+                                "the files written are STEM_mesh_<value>.ply / .stl and STEM_meshes.json (default: <stem of PRED> under the data directory)")
 
 
 def parse_cleaning_args(argv=None) -> argparse.Namespace:
@@ -111,45 +132,38 @@ def parse_cleaning_args(argv=None) -> argparse.Namespace:
     return args
 
 
-def get_2d_measuring_parser() -> argparse.ArgumentParser:
-    """PRED [--data_dir DIR] [--output STEM]: measure the objects of an existing label volume with the measure_* keys of the predict settings."""
-    parser = argparse.ArgumentParser(description="Measure the objects of a label volume: per connected component its voxels, centroid, "
-                                                 "bounding box, surface, principal axes (measure_* settings keys).")
-    parser.add_argument(cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), metavar="PRED",
-                        help="the label volume to measure")
-    parser.add_argument("--output", type=Path, default=None, metavar="STEM",
-                        help="the files written are STEM_objects.csv and STEM_objects.json (default: <stem of PRED> under the data directory)")
-    _add_data_dir(parser)
-    return parser
-
-
-def parse_measuring_args(argv=None) -> argparse.Namespace:
-    """The measure command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
-    parser = get_2d_measuring_parser()
+def _parse_stem_args(parser: argparse.ArgumentParser, argv) -> argparse.Namespace:
     args = parser.parse_args(argv)
     if args.output is not None and not args.output.resolve().parent.is_dir():
         parser.error(f"--output {args.output}: the directory {args.output.resolve().parent} does not exist")
     return args
 
 
-def get_2d_meshing_parser() -> argparse.ArgumentParser:
-    """PRED [--data_dir DIR] [--output STEM]: mesh the surfaces of an existing label volume with the mesh_* keys of the predict settings."""
-    parser = argparse.ArgumentParser(description="Export surface meshes of a label volume: per label value a closed surface net as binary "
-                                                 "PLY or STL (mesh_* settings keys).")
-    parser.add_argument(cfg.PREDICTION_ARG, type=existing_file_with_suffix(cfg.LABEL_DATA_EXT), metavar="PRED",
-                        help="the label volume to mesh")
-    parser.add_argument("--output", type=Path, default=None, metavar="STEM",
-                        help="the files written are STEM_mesh_<value>.ply / .stl and STEM_meshes.json (default: <stem of PRED> under the data directory)")
-    _add_data_dir(parser)
-    return parser
+def parse_measuring_args(argv=None) -> argparse.Namespace:
+    """The measure command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
+    return _parse_stem_args(get_2d_measuring_parser(), argv)
 
 
 def parse_meshing_args(argv=None) -> argparse.Namespace:
     """The mesh command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
-    parser = get_2d_meshing_parser()
-    args = parser.parse_args(argv)
-    if args.output is not None and not args.output.resolve().parent.is_dir():
-        parser.error(f"--output {args.output}: the directory {args.output.resolve().parent} does not exist")
+    return _parse_stem_args(get_2d_meshing_parser(), argv)
+
+
+def open_label_volume(parse, argv) -> argparse.Namespace:
+    """What the commands on an existing label volume do first: set up logging, parse with ``parse``, find the data directory, read the
+    predict settings where the file exists (else none are set) and the volume.  Returns the arguments with ``settings``,
+    ``settings_path``, ``pred_path``, ``pred``, ``chunking`` and ``stem`` - <stem of PRED> under the data directory - added."""
+    logging.basicConfig(level=logging.INFO, format=cfg.LOGGING_FMT, datefmt=cfg.LOGGING_DATE_FMT)
+    args = parse(argv)
+    root = root_path(args)
+    from types import SimpleNamespace
+    from ..data import get_settings_data
+    from . import base_data_utils as utils
+    args.pred_path = getattr(args, cfg.PREDICTION_ARG)
+    args.settings_path = root / cfg.SETTINGS_DIR / cfg.PREDICTION_SETTINGS_FN
+    args.settings = get_settings_data(args.settings_path) if args.settings_path.is_file() else SimpleNamespace()
+    args.pred, args.chunking = utils.get_numpy_from_path(args.pred_path, internal_path=getattr(args.settings, "data_hdf5_path", "/data"))
+    args.stem = root / args.pred_path.stem
     return args
 
 

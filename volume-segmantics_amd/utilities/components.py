@@ -26,8 +26,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import evaluation as ev
-from .surface_distance import _pick_device, _require_memory, _zyx
+from . import label_volume as lv
 
 TILE_Z, TILE_Y, TILE_X = 8, 8, 64      # csrc/components.hip kTZ / kTY / kTX: the tile a workgroup labels in LDS
 VOXEL_LIMIT = 1 << 31                  # component ids are int32 voxel indices
@@ -36,39 +35,13 @@ _RANK = {6: 1, 18: 2, 26: 3}           # non-zero offsets a neighbour may have
 
 # ---- arguments -------------------------------------------------------------------------------------------------------------------
 def _check(shape, connectivity) -> tuple[int, int, int]:
-    zyx = _zyx(shape)
+    zyx = lv.zyx(shape)
     if int(connectivity) not in _RANK:
         raise ValueError(f"connectivity {connectivity}: it is 6, 18 or 26")
     if zyx[0] * zyx[1] * zyx[2] >= VOXEL_LIMIT:
         raise ValueError(f"a volume of shape {tuple(shape)} holds {zyx[0] * zyx[1] * zyx[2]} voxels: components need fewer than 2^31 "
                          f"(ids are int32 voxel indices)")
     return zyx
-
-
-def _u8(vol):
-    """the volume as uint8 - a host array or a device tensor as it came - after checking that every value fits"""
-    if ev._is_tensor(vol):
-        import torch
-        if vol.dtype == torch.uint8:
-            return vol
-        if vol.dtype == torch.bool:
-            return vol.to(torch.uint8)
-        if vol.dtype.is_floating_point or vol.dtype.is_complex:
-            raise TypeError(f"expected an integer label volume, got {vol.dtype}")
-        lo, hi = int(vol.min()), int(vol.max())
-        if lo < 0 or hi > 255:
-            raise ValueError(f"label values {lo}..{hi} do not fit uint8")
-        return vol.to(torch.uint8)
-    a = np.asarray(vol)
-    if a.dtype == np.uint8:
-        return a
-    if a.dtype == np.bool_:
-        return a.astype(np.uint8)
-    if not np.issubdtype(a.dtype, np.integer):
-        raise TypeError(f"expected an integer label volume, got {a.dtype}")
-    if a.size and (int(a.min()) < 0 or int(a.max()) > 255):
-        raise ValueError(f"label values {int(a.min())}..{int(a.max())} do not fit uint8")
-    return a.astype(np.uint8)
 
 
 def _per_value(setting, cast, background: int, name: str) -> np.ndarray:
@@ -162,23 +135,13 @@ def _roots_host(vol: np.ndarray, connectivity: int, use_scipy=None) -> np.ndarra
     return _roots_scipy(vol, connectivity, ndimage) if ndimage is not None else _roots_numpy(vol, connectivity)
 
 
-def _touch_mask(zyx) -> np.ndarray:
-    face = np.zeros(zyx, dtype=bool)
-    for axis, extent in enumerate(zyx):
-        if extent > 1:
-            s = [slice(None)] * 3
-            s[axis] = [0, extent - 1]
-            face[tuple(s)] = True
-    return face
-
-
 def _table_host(vol: np.ndarray, comp: np.ndarray):
     """per component, roots ascending: root, size, value, touches, and the value and root of the voxel in front of the root"""
     flat_v, flat_c = vol.reshape(-1), comp.reshape(-1)
     size = np.bincount(flat_c, minlength=flat_c.size)
     roots = np.flatnonzero(size)
     touch = np.zeros(flat_c.size, dtype=bool)
-    touch[flat_c[_touch_mask(vol.shape).reshape(-1)]] = True
+    touch[flat_c[lv.touch_mask(vol.shape).reshape(-1)]] = True
     front = np.maximum(roots - 1, 0)
     return dict(roots=roots.astype(np.int64), sizes=size[roots].astype(np.int64), values=flat_v[roots].astype(np.int64), touches=touch[roots],
                 front_values=flat_v[front].astype(np.int64), front_roots=flat_c[front].astype(np.int64))
@@ -186,12 +149,14 @@ def _table_host(vol: np.ndarray, comp: np.ndarray):
 
 # ---- device routes ---------------------------------------------------------------------------------------------------------------
 def _device_bytes(zyx, on_device: bool) -> int:
+    """the upload unless the volume is there, the roots, sizes, touches, the cleaned copy and the workspace"""
     from .. import _lib
     n = zyx[0] * zyx[1] * zyx[2]
     return (0 if on_device else n) + 4 * n + 4 * n + n + n + int(_lib.lib.vs_components_workspace_bytes(*zyx))
 
 
-def _label_device(labels_dev, zyx, connectivity):
+def label_device(labels_dev, zyx, connectivity):
+    """vs_label_components on flat aligned device bytes: the int32 root of every voxel, on the device"""
     import torch
     from .. import _lib
     n = labels_dev.numel()
@@ -203,7 +168,8 @@ def _label_device(labels_dev, zyx, connectivity):
     return comp
 
 
-def _sizes_device(comp, zyx):
+def sizes_device(comp, zyx):
+    """vs_component_sizes: (int32 size, uint8 touches) at every root, 0 elsewhere, on the device"""
     import torch
     from .. import _lib
     size = torch.empty(comp.numel(), dtype=torch.int32, device=comp.device)
@@ -233,25 +199,19 @@ def _largest_device(labels_dev, size):
     return np.where(k != 0, 0x7FFFFFFF - (k & 0xFFFFFFFF), -1).astype(np.int64)
 
 
-def _prepare(vol, connectivity, device):
-    """(shape, zyx, device or None, the volume as a host (Z, Y, X) array or a flat aligned device tensor)"""
-    shape = tuple(vol.shape)
-    zyx = _check(shape, connectivity)
-    device = _pick_device(device, vol)
-    v = _u8(vol)
-    if device is None:
-        return shape, zyx, None, np.ascontiguousarray(ev._to_host(v)).reshape(zyx)
-    _require_memory(device, _device_bytes(zyx, ev._is_tensor(v) and v.is_cuda), f"the components of a {shape} volume")
-    return shape, zyx, device, ev._aligned_u8(v, device)
+def prepare(vol, connectivity, device):
+    """``label_volume.prepare`` after the checks of a labelling, with the device memory one takes: (shape, zyx, device or None, volume)"""
+    _check(tuple(vol.shape), connectivity)
+    return lv.prepare(vol, device, _device_bytes, "components")
 
 
 # ---- public: the pieces ------------------------------------------------------------------------------------------------------------
 def label_components(vol, connectivity: int = 6, device=None) -> np.ndarray:
     """int32 array of ``vol.shape``: for every voxel the root of its component (the linear index of the component's lowest voxel)."""
-    shape, zyx, device, v = _prepare(vol, connectivity, device)
+    shape, zyx, device, v = prepare(vol, connectivity, device)
     if device is None:
         return _roots_host(v, int(connectivity)).reshape(shape)
-    return _label_device(v, zyx, connectivity).cpu().numpy().reshape(shape)
+    return label_device(v, zyx, connectivity).cpu().numpy().reshape(shape)
 
 
 def _largest_of(table) -> np.ndarray:
@@ -267,12 +227,12 @@ def _largest_of(table) -> np.ndarray:
 
 def component_table(vol, connectivity: int = 6, device=None) -> dict:
     """``{label value: {"components": count, "sizes": [voxel counts, descending]}}`` for every value that occurs."""
-    _, zyx, device, v = _prepare(vol, connectivity, device)
+    _, zyx, device, v = prepare(vol, connectivity, device)
     if device is None:
         table = _table_host(v, _roots_host(v, int(connectivity)))
     else:
-        comp = _label_device(v, zyx, connectivity)
-        table = _table_device(v, comp, *_sizes_device(comp, zyx))
+        comp = label_device(v, zyx, connectivity)
+        table = _table_device(v, comp, *sizes_device(comp, zyx))
     out = {}
     for value in np.unique(table["values"]):
         sizes = np.sort(table["sizes"][table["values"] == value])[::-1]
@@ -332,7 +292,7 @@ def clean_label_volume(vol, min_object_size=0, keep_largest=False, fill_holes: i
         raise ValueError("fill_holes must not be negative")
     min_size = _per_value(min_object_size, int, background, "min_object_size")
     keep = _per_value(keep_largest, lambda x: int(bool(x)), background, "keep_largest") != 0
-    shape, zyx, device, v = _prepare(vol, connectivity, device)
+    shape, zyx, device, v = prepare(vol, connectivity, device)
     settings = dict(connectivity=connectivity, background=background, fill_holes=fill_holes,
                     min_object_size={str(c): int(min_size[c]) for c in np.flatnonzero(min_size)},
                     keep_largest=[int(c) for c in np.flatnonzero(keep)])
@@ -343,8 +303,8 @@ def clean_label_volume(vol, min_object_size=0, keep_largest=False, fill_holes: i
 
     import torch
     from .. import _lib
-    comp = _label_device(v, zyx, connectivity)
-    size, touches = _sizes_device(comp, zyx)
+    comp = label_device(v, zyx, connectivity)
+    size, touches = sizes_device(comp, zyx)
     keep_root = np.where(keep, _largest_device(v, size), -1)
     out = torch.empty_like(v)
     counts = torch.empty(4, dtype=torch.int64, device=device)

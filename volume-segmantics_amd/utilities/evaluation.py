@@ -15,9 +15,11 @@ from pathlib import Path
 
 import numpy as np
 
+from . import label_volume as lv
+
 KERNEL_MAX_CLASSES = 16       # vs_confusion_matrix: the pair code t * K + p is one byte
 MAX_CLASSES = 254             # class bytes 254 / 255 are the table's "invalid" / "ignore" marks
-_IGNORE, _INVALID = 255, 254
+IGNORE, INVALID = 255, 254
 
 
 @dataclass
@@ -98,7 +100,7 @@ def truth_label_values(label_codes, truth, classes: int, ignore_label=None, labe
             if found:
                 values = np.unique(np.asarray(found, dtype=np.int64))
         if values is None:
-            values = np.unique(_to_host(truth)).astype(np.int64)
+            values = np.unique(lv.to_host(truth)).astype(np.int64)
             if ignore_label is not None:
                 values = values[values != int(ignore_label)]
     if len(values) > classes:
@@ -107,53 +109,32 @@ def truth_label_values(label_codes, truth, classes: int, ignore_label=None, labe
 
 
 # ---- counting ------------------------------------------------------------------------------------------------------------
-def _is_tensor(x) -> bool:
-    return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
-
-
-def _to_host(x) -> np.ndarray:
-    return x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-
-
-def _truth_table(classes: int, label_values, ignore_label) -> np.ndarray:
+def truth_table(classes: int, label_values, ignore_label) -> np.ndarray:
     """raw ground-truth byte -> class index (255 ignore, 254 invalid)"""
-    lut = np.full(256, _INVALID, dtype=np.uint8)
+    lut = np.full(256, INVALID, dtype=np.uint8)
     values = np.arange(classes) if label_values is None else np.asarray(label_values, dtype=np.int64)
     for i, v in enumerate(values):
         if 0 <= int(v) <= 255:
             lut[int(v)] = i
     if ignore_label is not None and 0 <= int(ignore_label) <= 255:
-        lut[int(ignore_label)] = _IGNORE
+        lut[int(ignore_label)] = IGNORE
     return lut
 
 
-def _wide_truth_to_classes(truth: np.ndarray, classes: int, label_values, ignore_label) -> np.ndarray:
+def wide_truth_to_classes(truth: np.ndarray, classes: int, label_values, ignore_label) -> np.ndarray:
     """ground truth of a wider integer dtype -> uint8 class indices (255 ignore, 254 invalid) on the host"""
     values = np.arange(classes, dtype=np.int64) if label_values is None else np.asarray(label_values, dtype=np.int64)
     order = np.argsort(values, kind="stable")
     sorted_values = values[order]
     flat = truth.reshape(-1).astype(np.int64, copy=False)
-    out = np.full(flat.shape, _INVALID, dtype=np.uint8)
+    out = np.full(flat.shape, INVALID, dtype=np.uint8)
     if len(values):
         pos = np.clip(np.searchsorted(sorted_values, flat), 0, len(values) - 1)
         hit = sorted_values[pos] == flat
         out[hit] = order[pos[hit]].astype(np.uint8)
     if ignore_label is not None:
-        out[flat == int(ignore_label)] = _IGNORE
+        out[flat == int(ignore_label)] = IGNORE
     return out.reshape(truth.shape)
-
-
-def _pred_to_bytes(pred: np.ndarray) -> np.ndarray:
-    """predictions of a wider integer dtype -> uint8; whatever does not fit becomes 255, which no class count reaches"""
-    if pred.dtype == np.uint8:
-        return pred
-    if pred.dtype == np.bool_:
-        return pred.astype(np.uint8)
-    if not np.issubdtype(pred.dtype, np.integer):
-        raise TypeError(f"predictions must be an integer label volume, got {pred.dtype}")
-    out = pred.astype(np.uint8)
-    out[(pred < 0) | (pred > 254)] = 255
-    return out
 
 
 def _count_numpy(t: np.ndarray, p: np.ndarray, lut: np.ndarray, classes: int, nslabs: int):
@@ -164,7 +145,7 @@ def _count_numpy(t: np.ndarray, p: np.ndarray, lut: np.ndarray, classes: int, ns
     for s in range(nslabs):
         tc = lut[t[s]].astype(np.int64)
         ps = p[s].astype(np.int64)
-        ignored = tc == _IGNORE
+        ignored = tc == IGNORE
         invalid = ~ignored & ((tc >= classes) | (ps >= classes))
         code = np.where(ignored, k2, np.where(invalid, k2 + 1, tc * classes + ps))
         b = np.bincount(code, minlength=k2 + 2)
@@ -179,20 +160,12 @@ def _count_torch(t, p, lut: np.ndarray, classes: int, nslabs: int):
     k2 = classes * classes
     tc = torch.from_numpy(lut).to(t.device)[t.reshape(-1).long()].long()
     ps = p.reshape(-1).long()
-    ignored = tc == _IGNORE
+    ignored = tc == IGNORE
     invalid = ~ignored & ((tc >= classes) | (ps >= classes))
     code = torch.where(ignored, k2, torch.where(invalid, k2 + 1, tc * classes + ps))
     slab = torch.arange(nslabs, device=t.device).repeat_interleave(t.numel() // nslabs)
     b = torch.bincount(code + slab * (k2 + 2), minlength=nslabs * (k2 + 2)).reshape(nslabs, k2 + 2).cpu().numpy().astype(np.int64)
     return b[:, :k2].reshape(nslabs, classes, classes).copy(), b[:, k2:].copy()
-
-
-def _aligned_u8(x, device):
-    """the volume as flat, contiguous, 16-byte aligned uint8 device memory"""
-    import torch
-
-    x = (x if _is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device).contiguous().reshape(-1)
-    return x if x.data_ptr() % 16 == 0 else x.clone()
 
 
 def _count_kernel(t, p, lut: np.ndarray, classes: int, nslabs: int):
@@ -249,37 +222,30 @@ def confusion_matrix(pred, truth, classes: int, *, label_values=None, ignore_lab
     if label_values is not None and len(label_values) > classes:
         raise ValueError(f"{len(label_values)} label values for {classes} classes")
 
-    import torch
-    if device is None:
-        src = pred if _is_tensor(pred) and pred.is_cuda else truth if _is_tensor(truth) and truth.is_cuda else None
-        device = src.device if src is not None else (torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
-    device = None if device is None else torch.device(device)
-    on_gpu = device is not None and device.type == "cuda"
+    device = lv.pick_device(device, pred, truth)
 
     # normal form of all three routes: uint8 truth + a 256-entry table, uint8 predictions
-    truth_is_u8 = (truth.dtype == torch.uint8) if _is_tensor(truth) else (np.asarray(truth).dtype == np.uint8)
-    if truth_is_u8:
-        t, lut = truth, _truth_table(classes, label_values, ignore_label)
+    if lv.is_u8(truth):
+        t, lut = truth, truth_table(classes, label_values, ignore_label)
     else:
-        th = _to_host(truth)
+        th = lv.to_host(truth)
         if th.dtype != np.bool_ and not np.issubdtype(th.dtype, np.integer):
             raise TypeError(f"ground truth must be an integer label volume, got {th.dtype}")
-        t = _wide_truth_to_classes(th, classes, label_values, ignore_label)
+        t = wide_truth_to_classes(th, classes, label_values, ignore_label)
         lut = np.arange(256, dtype=np.uint8)
-        lut[classes:_INVALID] = _INVALID
-    pred_is_u8 = (pred.dtype == torch.uint8) if _is_tensor(pred) else (np.asarray(pred).dtype == np.uint8)
-    p = pred if pred_is_u8 else _pred_to_bytes(_to_host(pred))
+        lut[classes:INVALID] = INVALID
+    p = lv.lenient_u8(pred)
 
-    if not on_gpu:
-        counts, dropped = _count_numpy(np.ascontiguousarray(_to_host(t)), np.ascontiguousarray(_to_host(p)), lut, classes, nslabs)
+    if device is None:
+        counts, dropped = _count_numpy(np.ascontiguousarray(lv.to_host(t)), np.ascontiguousarray(lv.to_host(p)), lut, classes, nslabs)
     else:
-        td, pd = _aligned_u8(t, device), _aligned_u8(p, device)
+        td, pd = lv.aligned_u8(t, device), lv.aligned_u8(p, device)
         route = _count_kernel if classes <= KERNEL_MAX_CLASSES else _count_torch
         counts, dropped = route(td, pd, lut, classes, nslabs)
     invalid = int(dropped[:, 1].sum())
     if invalid:
         raise ValueError(f"{invalid} of {n} voxels cannot be scored: "
-                         + _describe_invalid(_to_host(truth), _to_host(pred), classes, label_values, ignore_label))
+                         + _describe_invalid(lv.to_host(truth), lv.to_host(pred), classes, label_values, ignore_label))
     return (counts, dropped) if per_slice else (counts[0], dropped[0])
 
 
@@ -298,11 +264,6 @@ def score_table(scores: SegmentationScores, label_values=None) -> str:
                      f"{scores.recall[i]:>8.5f}")
     lines.append(f"mean over the classes present: dice {scores.mean_dice:.5f}, iou {scores.mean_iou:.5f}; voxel accuracy {scores.accuracy:.5f}")
     return "\n".join(lines)
-
-
-def _json_number(x):
-    x = float(x)
-    return None if np.isnan(x) else x
 
 
 def write_scores(stem, scores: SegmentationScores, dropped, label_values=None, slab_dice=None) -> list[Path]:
@@ -326,9 +287,9 @@ def write_scores(stem, scores: SegmentationScores, dropped, label_values=None, s
     dropped = np.asarray(dropped).reshape(-1, 2).sum(0)
     doc = {"classes": [dict(index=i, label_value=values[i], truth_voxels=int(scores.truth_voxels[i]),
                             predicted_voxels=int(scores.predicted_voxels[i]), true_positives=int(scores.true_positives[i]),
-                            dice=_json_number(scores.dice[i]), iou=_json_number(scores.iou[i]),
-                            precision=_json_number(scores.precision[i]), recall=_json_number(scores.recall[i])) for i in range(k)],
-           "mean_dice": _json_number(scores.mean_dice), "mean_iou": _json_number(scores.mean_iou), "accuracy": _json_number(scores.accuracy),
+                            dice=lv.json_number(scores.dice[i]), iou=lv.json_number(scores.iou[i]),
+                            precision=lv.json_number(scores.precision[i]), recall=lv.json_number(scores.recall[i])) for i in range(k)],
+           "mean_dice": lv.json_number(scores.mean_dice), "mean_iou": lv.json_number(scores.mean_iou), "accuracy": lv.json_number(scores.accuracy),
            "confusion_matrix": scores.confusion.tolist(), "dropped": {"ignored": int(dropped[0]), "invalid": int(dropped[1])}}
     with open(written[1], "w") as f:
         json.dump(doc, f, indent=1)

@@ -24,8 +24,7 @@ from pathlib import Path
 import numpy as np
 
 from . import components as co
-from . import evaluation as ev
-from .surface_distance import _require_memory, _zyx
+from . import label_volume as lv
 
 FIELDS = ("voxels", "sum_z", "sum_y", "sum_x", "sum_zz", "sum_yy", "sum_xx", "sum_zy", "sum_zx", "sum_yx",
           "min_z", "max_z", "min_y", "max_y", "min_x", "max_x", "faces_z", "faces_y", "faces_x", "touches_border")      # csrc/measure.hip kFields
@@ -35,7 +34,7 @@ SUM_LIMIT = 1 << 63
 
 # ---- arguments -------------------------------------------------------------------------------------------------------------------
 def _check_sums_fit(shape) -> None:
-    zyx = _zyx(shape)
+    zyx = lv.zyx(shape)
     n, longest = zyx[0] * zyx[1] * zyx[2], max(zyx)
     if n * (longest - 1) ** 2 >= SUM_LIMIT:
         raise ValueError(f"a volume of shape {tuple(shape)} can hold a sum of squared coordinates of {n} x {longest - 1}^2, which does not "
@@ -49,16 +48,6 @@ def _arguments(min_voxels, background):
     if not 0 <= background <= 255:
         raise ValueError(f"background {background} is not a uint8 value")
     return min_voxels, background
-
-
-def _voxel_size(voxel_size) -> tuple[float, float, float]:
-    """a scalar or [sz, sy, sx], each positive"""
-    size = np.asarray(voxel_size, dtype=np.float64).reshape(-1)
-    if size.size == 1:
-        size = np.repeat(size, 3)
-    if size.size != 3 or not np.all(np.isfinite(size)) or not np.all(size > 0):
-        raise ValueError(f"voxel size {voxel_size!r}: it is one positive number or three, [sz, sy, sx]")
-    return float(size[0]), float(size[1]), float(size[2])
 
 
 # ---- host route ------------------------------------------------------------------------------------------------------------------
@@ -103,12 +92,12 @@ def _table_host(vol: np.ndarray, comp: np.ndarray, row_of_root: np.ndarray, rows
         table[:, F["min_" + letter]] = np.minimum.reduceat(coord, starts)
         table[:, F["max_" + letter]] = np.maximum.reduceat(coord, starts)
         table[:, F["faces_" + letter]] = np.add.reduceat(_exposed_host(vol, axis).reshape(-1)[order].astype(np.int64), starts)
-    table[:, F["touches_border"]] = np.maximum.reduceat(co._touch_mask(vol.shape).reshape(-1)[order].astype(np.int64), starts)
+    table[:, F["touches_border"]] = np.maximum.reduceat(lv.touch_mask(vol.shape).reshape(-1)[order].astype(np.int64), starts)
     return table
 
 
 def _measure_host(vol: np.ndarray, connectivity: int, min_voxels: int, background: int, include_background: bool, want_ids: bool):
-    comp = co._roots_host(vol, connectivity)
+    comp = co.label_components(vol, connectivity, device="cpu")
     flat_c = comp.reshape(-1)
     size = np.bincount(flat_c, minlength=flat_c.size)
     roots = np.flatnonzero(size).astype(np.int64)
@@ -138,9 +127,9 @@ def _moments_device(labels_dev, comp, row_of_root, zyx, rows: int):
 def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, background: int, include_background: bool, want_ids: bool):
     import torch
     n = v.numel()
-    _require_memory(device, 4 * n + (4 * n if want_ids else 0), f"the row of every root of a {tuple(zyx)} volume")
-    comp = co._label_device(v, zyx, connectivity)
-    size, _ = co._sizes_device(comp, zyx)
+    lv.require_memory(device, 4 * n + (4 * n if want_ids else 0), f"the row of every root of a {tuple(zyx)} volume")
+    comp = co.label_device(v, zyx, connectivity)
+    size, _ = co.sizes_device(comp, zyx)
     roots = torch.nonzero(size).reshape(-1)                           # ascending
     sizes, values = size[roots].to(torch.int64), v[roots].to(torch.int64)
     del size
@@ -152,7 +141,7 @@ def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, backgrou
     values, order = torch.sort(values[keep], stable=True)             # by value; roots stay ascending within a value
     roots = roots[keep][order]
     rows = int(roots.numel())
-    _require_memory(device, 8 * len(FIELDS) * rows, f"the table of {rows} components")
+    lv.require_memory(device, 8 * len(FIELDS) * rows, f"the table of {rows} components")
     row_of_root = torch.full((n,), -1, dtype=torch.int32, device=device)
     row_of_root[roots] = torch.arange(rows, dtype=torch.int32, device=device)
     table = _moments_device(v, comp, row_of_root, zyx, rows)
@@ -165,7 +154,7 @@ def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, backgrou
 def _measure(vol, connectivity, min_voxels, background, include_background, device, want_ids):
     _check_sums_fit(vol.shape)
     min_voxels, background = _arguments(min_voxels, background)
-    shape, zyx, device, v = co._prepare(vol, connectivity, device)
+    shape, zyx, device, v = co.prepare(vol, connectivity, device)
     if device is None:
         raw, ids = _measure_host(v, int(connectivity), min_voxels, background, bool(include_background), want_ids)
     else:
@@ -223,8 +212,8 @@ def object_table(raw: dict, voxel_size=1.0, shape=None) -> dict:
     object in a viewer.  The summary holds per value the objects, voxels, volume, volume fraction of the whole volume, the largest
     and the median object (voxels) and the components that were not listed."""
     table = np.asarray(raw["table"], dtype=np.int64).reshape(-1, len(FIELDS))
-    zyx = _zyx(tuple(int(s) for s in (raw["shape"] if shape is None else shape)))
-    sz, sy, sx = _voxel_size(voxel_size)
+    zyx = lv.zyx(tuple(int(s) for s in (raw["shape"] if shape is None else shape)))
+    sz, sy, sx = lv.voxel_size(voxel_size)
     roots, values = np.asarray(raw["roots"], dtype=np.int64), np.asarray(raw["values"], dtype=np.int64)
     col = lambda name: table[:, F[name]]                              # noqa: E731
     n = col("voxels").astype(np.float64)
@@ -281,7 +270,7 @@ def measurement_settings(settings) -> dict:
     voxel_size = getattr(settings, "measure_voxel_size", None)
     return dict(active=bool(getattr(settings, "measure_objects", False)), connectivity=connectivity, min_voxels=min_voxels,
                 include_background=bool(getattr(settings, "measure_background", False)),
-                voxel_size=list(_voxel_size(1.0 if voxel_size is None else voxel_size)), save_ids=bool(getattr(settings, "measure_save_ids", False)))
+                voxel_size=list(lv.voxel_size(1.0 if voxel_size is None else voxel_size)), save_ids=bool(getattr(settings, "measure_save_ids", False)))
 
 
 def measure_label_volume(vol, settings, device=None) -> dict:
@@ -329,9 +318,9 @@ def write_measurements(stem, raw: dict, table: dict, settings: dict | None = Non
             w.writerow([cell(name, i) if name in _INT_COLUMNS else repr(cell(name, i)) for name in COLUMNS])
     raw_table = np.asarray(raw["table"], dtype=np.int64).reshape(-1, len(FIELDS))
     doc = {"settings": settings, "shape": table["shape"], "voxel_size": table["voxel_size"], "fields": list(FIELDS),
-           "summary": {value: {k: (ev._json_number(x) if isinstance(x, float) else x) for k, x in row.items()} for value, row in table["summary"].items()},
+           "summary": {value: {k: (lv.json_number(x) if isinstance(x, float) else x) for k, x in row.items()} for value, row in table["summary"].items()},
            "objects": [{"id": int(o["id"][i]), "value": int(o["value"][i]), "root": int(o["root"][i]), "raw": [int(x) for x in raw_table[i]],
-                        "derived": {name: ev._json_number(o[name][i]) for name in COLUMNS if name not in _INT_COLUMNS}} for i in range(rows)]}
+                        "derived": {name: lv.json_number(o[name][i]) for name in COLUMNS if name not in _INT_COLUMNS}} for i in range(rows)]}
     with open(written[1], "w") as f:
         json.dump(doc, f, indent=1)
     return written

@@ -29,9 +29,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import components as co
-from . import evaluation as ev
-from .surface_distance import _pick_device, _require_memory, _zyx
+from . import label_volume as lv
 
 STYLES = {"smooth": 0, "blocky": 1}            # include/volseg_hip.h VS_MESH_SMOOTH / VS_MESH_BLOCKY
 FORMATS = ("ply", "stl")
@@ -41,7 +39,7 @@ AXES = ("z", "y", "x")
 
 # ---- arguments -------------------------------------------------------------------------------------------------------------------
 def _check(shape, value, style) -> tuple[tuple[int, int, int], int, str]:
-    zyx = _zyx(shape)
+    zyx = lv.zyx(shape)
     cells = (zyx[0] + 1) * (zyx[1] + 1) * (zyx[2] + 1)
     if cells >= CELL_LIMIT:
         raise ValueError(f"a volume of shape {tuple(shape)} has {cells} cells: a mesh needs fewer than 2^31 (vertex ids are int32)")
@@ -117,7 +115,7 @@ def _surface_device(labels_dev, zyx, value: int, style: str):
     from .. import _lib
     device = labels_dev.device
     need = int(_lib.lib.vs_mesh_workspace_bytes(*zyx))
-    _require_memory(device, need + 32, f"the mesh workspace of a {tuple(zyx)} volume")
+    lv.require_memory(device, need + 32, f"the mesh workspace of a {tuple(zyx)} volume")
     work = torch.empty(need, dtype=torch.uint8, device=device)
     totals = torch.empty(4, dtype=torch.int64, device=device)
     with torch.cuda.device(device):
@@ -125,7 +123,7 @@ def _surface_device(labels_dev, zyx, value: int, style: str):
         counts = [int(t) for t in totals.cpu()]
         n_vertices, n_quads = counts[0], sum(counts[1:])
         _check_counts(n_vertices, counts[1:])
-        _require_memory(device, 12 * n_vertices + 16 * n_quads, f"the {n_vertices} vertices and {n_quads} quads of value {value}")
+        lv.require_memory(device, 12 * n_vertices + 16 * n_quads, f"the {n_vertices} vertices and {n_quads} quads of value {value}")
         vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=device)
         quads = torch.empty((n_quads, 4), dtype=torch.int32, device=device)
         if n_vertices or n_quads:
@@ -136,19 +134,14 @@ def _surface_device(labels_dev, zyx, value: int, style: str):
 
 # ---- public: the arrays ------------------------------------------------------------------------------------------------------------
 def _labels(vol, device):
-    """(zyx checked later, device or None, the volume as a host array or a flat aligned device tensor)"""
-    device = _pick_device(device, vol)
-    v = co._u8(vol)
-    if device is None:
-        return None, np.ascontiguousarray(ev._to_host(v))
-    if not (ev._is_tensor(v) and v.is_cuda):
-        _require_memory(device, int(np.prod(tuple(v.shape))), f"the labels of a {tuple(v.shape)} volume")
-    return device, ev._aligned_u8(v, device)
+    """(device or None, the volume as a host (Z, Y, X) array or a flat aligned device tensor); the upload is all the memory asked for here"""
+    _, _, device, v = lv.prepare(vol, device, lambda zyx, resident: 0 if resident else int(np.prod(zyx)), "labels")
+    return device, v
 
 
 def _extract(v, zyx, device, value: int, style: str) -> dict:
     if device is None:
-        vertices, quads, per_axis = _surface_host(v.reshape(zyx), value, style)
+        vertices, quads, per_axis = _surface_host(v, value, style)
         _check_counts(len(vertices), per_axis)
     else:
         vertices, quads, per_axis = _surface_device(v, zyx, value, style)
@@ -165,14 +158,9 @@ def extract_surface(vol, value, style: str = "smooth", device=None) -> dict:
 
 
 # ---- public: the figures -----------------------------------------------------------------------------------------------------------
-def _voxel_size(voxel_size) -> tuple[float, float, float]:
-    from .measurements import _voxel_size as parse
-    return parse(voxel_size)
-
-
 def _positions_xyz(vertices, voxel_size) -> np.ndarray:
     """(V, 3) float64 right-handed (x, y, z) in physical units"""
-    sz, sy, sx = _voxel_size(voxel_size)
+    sz, sy, sx = lv.voxel_size(voxel_size)
     p = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
     return np.stack([p[:, 2] * sx, p[:, 1] * sy, p[:, 0] * sz], axis=1)
 
@@ -191,7 +179,7 @@ def mesh_summary(surface: dict, voxel_size=1.0) -> dict:
     ``bounding_box`` [[z, y, x] min, [z, y, x] max] in physical units, None for an empty mesh."""
     quads = np.asarray(surface["quads"], dtype=np.int64).reshape(-1, 4)
     per_axis = [int(q) for q in surface["quads_per_axis"]]
-    sz, sy, sx = _voxel_size(voxel_size)
+    sz, sy, sx = lv.voxel_size(voxel_size)
     p = _positions_xyz(surface["vertices"], (sz, sy, sx))
     n_vertices = len(p)
     tri = triangles_of(quads)
@@ -273,7 +261,7 @@ def mesh_settings(settings) -> dict:
     if voxel_size is None:
         voxel_size = getattr(settings, "measure_voxel_size", None)
     return dict(active=bool(getattr(settings, "mesh_surfaces", False)), values=values, style=style, format=fmt,
-                triangulate=bool(getattr(settings, "mesh_triangulate", False)), voxel_size=list(_voxel_size(1.0 if voxel_size is None else voxel_size)))
+                triangulate=bool(getattr(settings, "mesh_triangulate", False)), voxel_size=list(lv.voxel_size(1.0 if voxel_size is None else voxel_size)))
 
 
 def mesh_label_volume(vol, settings, device=None) -> dict:
@@ -294,7 +282,7 @@ def mesh_label_volume(vol, settings, device=None) -> dict:
 def _bincount_device(v) -> np.ndarray:
     """256 counts: which values occur"""
     import torch
-    _require_memory(v.device, 8 * 256, "the histogram of the label values")
+    lv.require_memory(v.device, 8 * 256, "the histogram of the label values")
     return torch.bincount(v, minlength=256).cpu().numpy()
 
 

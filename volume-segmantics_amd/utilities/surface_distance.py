@@ -19,20 +19,15 @@ from pathlib import Path
 import numpy as np
 
 from . import evaluation as ev
+from . import label_volume as lv
 
 INF_D2 = 0xFFFFFFFF           # d2 of every voxel when there is no seed
 EDT_LDS_MAX_AXIS = 512        # csrc/surface.hip kMaxLdsAxis: the longest y / z axis a workgroup's LDS tile holds
 _DIRECTIONS = ("truth_to_pred", "pred_to_truth")
+_zyx = lv.zyx                 # the shared shape rule under the name this module and its GPU tests have always used
 
 
-# ---- shapes and devices ----------------------------------------------------------------------------------------------------------
-def _zyx(shape) -> tuple[int, int, int]:
-    shape = tuple(int(s) for s in shape)
-    if not 1 <= len(shape) <= 3 or any(s < 1 for s in shape):
-        raise ValueError(f"expected a non-empty volume of one to three dimensions, got shape {shape}")
-    return (1,) * (3 - len(shape)) + shape
-
-
+# ---- shapes --------------------------------------------------------------------------------------------------------------------
 def histogram_bins(shape) -> int:
     """(Z-1)^2 + (Y-1)^2 + (X-1)^2 + 2: every squared distance the volume can hold, then the bin of the 0xFFFFFFFF voxels"""
     z, y, x = _zyx(shape)
@@ -40,22 +35,6 @@ def histogram_bins(shape) -> int:
     if most >= INF_D2:
         raise ValueError(f"a volume of shape {tuple(shape)} can hold a squared distance of {most}, which does not fit below 2^32 - 1")
     return most + 2
-
-
-def _pick_device(device, *arrays):
-    import torch
-    if device is None:
-        src = next((a for a in arrays if ev._is_tensor(a) and a.is_cuda), None)
-        device = src.device if src is not None else (torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else None)
-    device = None if device is None else torch.device(device)
-    return device if device is not None and device.type == "cuda" else None
-
-
-def _require_memory(device, need: int, what: str) -> None:
-    import torch
-    free, _ = torch.cuda.mem_get_info(device)
-    if need > free:
-        raise ValueError(f"{what} needs {need} bytes of device memory but only {free} bytes are free on {device}")
 
 
 # ---- host routes -----------------------------------------------------------------------------------------------------------------
@@ -110,10 +89,6 @@ def _histogram_host(surface: np.ndarray, d2: np.ndarray, bins: int) -> np.ndarra
 
 
 # ---- device routes ---------------------------------------------------------------------------------------------------------------
-def _device_u8(x, device):
-    return ev._aligned_u8(x, device)
-
-
 def _edt_device(seeds_dev, zyx, d2_dev, workspace):
     import torch
     from .. import _lib
@@ -144,16 +119,16 @@ def squared_distance_transform(seeds, device=None) -> np.ndarray:
     shape = tuple(seeds.shape)
     zyx = _zyx(shape)
     histogram_bins(shape)        # raises when a squared distance would not fit
-    device = _pick_device(device, seeds)
+    device = lv.pick_device(device, seeds)
     if device is None:
-        return _edt_host(ev._to_host(seeds)).reshape(shape)
+        return _edt_host(lv.to_host(seeds)).reshape(shape)
     n = int(np.prod(zyx))
     from .. import _lib
-    _require_memory(device, 5 * n + int(_lib.lib.vs_edt_workspace_bytes(*zyx)), f"the distance transform of a {shape} volume")
-    s = seeds if ev._is_tensor(seeds) else torch.from_numpy(np.ascontiguousarray(np.asarray(seeds) != 0).view(np.uint8))
+    lv.require_memory(device, 5 * n + int(_lib.lib.vs_edt_workspace_bytes(*zyx)), f"the distance transform of a {shape} volume")
+    s = seeds if lv.is_tensor(seeds) else torch.from_numpy(np.ascontiguousarray(np.asarray(seeds) != 0).view(np.uint8))
     if s.dtype != torch.uint8:
         s = (s != 0).to(torch.uint8)
-    s = _device_u8(s, device)
+    s = lv.aligned_u8(s, device)
     d2 = torch.empty(n, dtype=torch.int32, device=device)
     _edt_device(s, zyx, d2, _workspace(zyx, device))
     return d2.cpu().numpy().view(np.uint32).reshape(shape)
@@ -161,22 +136,20 @@ def squared_distance_transform(seeds, device=None) -> np.ndarray:
 
 def _class_bytes(labels, label_values, ignore_label):
     """(uint8 volume - host array or device tensor -, 256-entry table byte -> class with 255 = ignore, 254 = no class)"""
-    import torch
-    is_u8 = (labels.dtype == torch.uint8) if ev._is_tensor(labels) else (np.asarray(labels).dtype == np.uint8)
-    if is_u8:
+    if lv.is_u8(labels):
         lut = np.arange(256, dtype=np.uint8)
-        lut[254:] = ev._INVALID
+        lut[254:] = ev.INVALID
         if label_values is not None:
-            lut = ev._truth_table(len(label_values), label_values, None)
+            lut = ev.truth_table(len(label_values), label_values, None)
         if ignore_label is not None and 0 <= int(ignore_label) <= 255:
-            lut[int(ignore_label)] = ev._IGNORE
+            lut[int(ignore_label)] = ev.IGNORE
         return labels, lut
-    host = ev._to_host(labels)
+    host = lv.to_host(labels)
     if host.dtype == np.bool_:
         host = host.astype(np.uint8)
     if not np.issubdtype(host.dtype, np.integer):
         raise TypeError(f"expected an integer label volume, got {host.dtype}")
-    return ev._wide_truth_to_classes(host, 254, label_values, ignore_label), np.arange(256, dtype=np.uint8)
+    return ev.wide_truth_to_classes(host, 254, label_values, ignore_label), np.arange(256, dtype=np.uint8)
 
 
 def label_surface(labels, cls: int, *, label_values=None, ignore_label=None, device=None) -> np.ndarray:
@@ -189,12 +162,12 @@ def label_surface(labels, cls: int, *, label_values=None, ignore_label=None, dev
     shape = tuple(labels.shape)
     zyx = _zyx(shape)
     volume, lut = _class_bytes(labels, label_values, ignore_label)
-    device = _pick_device(device, labels)
+    device = lv.pick_device(device, labels)
     if device is None:
-        return _surface_host(lut[np.ascontiguousarray(ev._to_host(volume))] == cls).astype(np.uint8).reshape(shape)
+        return _surface_host(lut[np.ascontiguousarray(lv.to_host(volume))] == cls).astype(np.uint8).reshape(shape)
     n = int(np.prod(zyx))
-    _require_memory(device, 2 * n, f"the surface of a {shape} volume")
-    v = _device_u8(volume, device)
+    lv.require_memory(device, 2 * n, f"the surface of a {shape} volume")
+    v = lv.aligned_u8(volume, device)
     out = torch.empty(n, dtype=torch.uint8, device=device)
     _surface_device(v, torch.from_numpy(lut).to(device), cls, zyx, out)
     return out.cpu().numpy().reshape(shape)
@@ -218,16 +191,14 @@ def surface_distance_histograms(pred, truth, classes, *, label_values=None, igno
     if not class_list or min(class_list) < 0 or max(class_list) > 253:
         raise ValueError(f"classes must be 0..253, got {class_list[:20]}")
     t, lut = _class_bytes(truth, label_values, ignore_label)
-    import torch
-    pred_is_u8 = (pred.dtype == torch.uint8) if ev._is_tensor(pred) else (np.asarray(pred).dtype == np.uint8)
-    p = pred if pred_is_u8 else ev._pred_to_bytes(ev._to_host(pred))
-    device = _pick_device(device, pred, truth)
+    p = lv.lenient_u8(pred)
+    device = lv.pick_device(device, pred, truth)
     full = np.zeros((len(class_list), 2, bins), dtype=np.int64)
 
     if device is None:
-        tc = lut[np.ascontiguousarray(ev._to_host(t))].reshape(zyx)
-        ph = np.ascontiguousarray(ev._to_host(p)).reshape(zyx)
-        ignored = tc == ev._IGNORE
+        tc = lut[np.ascontiguousarray(lv.to_host(t))].reshape(zyx)
+        ph = np.ascontiguousarray(lv.to_host(p)).reshape(zyx)
+        ignored = tc == ev.IGNORE
         for i, c in enumerate(class_list):
             sa, sb = _surface_host(tc == c), _surface_host((ph == c) & ~ignored)
             if sa.any():
@@ -235,12 +206,13 @@ def surface_distance_histograms(pred, truth, classes, *, label_values=None, igno
             if sb.any():
                 full[i, 1] = _histogram_host(sb, _edt_host(sa), bins)
     else:
+        import torch
         from .. import _lib
         work = int(_lib.lib.vs_edt_workspace_bytes(*zyx))
         need = 2 * n + 4 * n + work + 8 * bins + (2 * n if ignore_label is not None else 0)
-        need += sum(n for x in (t, p) if not (ev._is_tensor(x) and x.is_cuda and x.device == device))
-        _require_memory(device, need, f"surface distances of a {shape} volume")
-        td, pd = _device_u8(t, device), _device_u8(p, device)
+        need += sum(n for x in (t, p) if not lv.is_resident(x, device))
+        lv.require_memory(device, need, f"surface distances of a {shape} volume")
+        td, pd = lv.aligned_u8(t, device), lv.aligned_u8(p, device)
         lut_dev = torch.from_numpy(lut).to(device)
         if ignore_label is not None:       # a voxel whose truth is ignored is in no predicted class either
             ignored = _ignored_mask(td, lut)
@@ -273,7 +245,7 @@ def _ignored_mask(truth_dev, lut: np.ndarray):
     """truth bytes that the table marks as ignored, without an int64 index volume: the ignore mark sits on few byte values"""
     import torch
     mask = torch.zeros_like(truth_dev, dtype=torch.bool)
-    for value in np.flatnonzero(lut == ev._IGNORE):
+    for value in np.flatnonzero(lut == ev.IGNORE):
         mask |= truth_dev == int(value)
     return mask
 
@@ -363,11 +335,6 @@ _COLUMNS = ("truth_surface_voxels", "predicted_surface_voxels", "hausdorff", "ha
 _INTEGER = {"truth_surface_voxels", "predicted_surface_voxels", "truth_within_tolerance", "predicted_within_tolerance"}
 
 
-def _json_number(x):
-    x = float(x)
-    return None if np.isnan(x) else "inf" if np.isinf(x) else x
-
-
 def surface_score_table(scores: SurfaceScores, label_values=None) -> str:
     """the per-class table as text, for the log"""
     values = list(range(scores.classes)) if label_values is None else [int(v) for v in label_values]
@@ -403,15 +370,15 @@ def write_surface_scores(stem, scores: SurfaceScores, hists, inf_counts, label_v
     for i in range(k):
         entry = dict(index=i, label_value=values[i])
         for c in _COLUMNS:
-            entry[c] = int(getattr(scores, c)[i]) if c in _INTEGER else _json_number(getattr(scores, c)[i])
+            entry[c] = int(getattr(scores, c)[i]) if c in _INTEGER else lv.json_number(getattr(scores, c)[i])
         entry["histograms"] = {}
         for d, name in enumerate(_DIRECTIONS):
             used = np.flatnonzero(h[i, d])
             entry["histograms"][name] = {"squared_distance": used.tolist(), "count": h[i, d, used].tolist(), "unreached": int(inf[i, d])}
         per_class.append(entry)
     doc = {"classes": per_class, "surface_tolerance": scores.tolerance, "voxel_size": scores.voxel_size,
-           "mean_hausdorff": _json_number(scores.mean_hausdorff), "mean_hausdorff_95": _json_number(scores.mean_hausdorff_95),
-           "mean_assd": _json_number(scores.mean_assd), "mean_surface_dice": _json_number(scores.mean_surface_dice)}
+           "mean_hausdorff": lv.json_number(scores.mean_hausdorff), "mean_hausdorff_95": lv.json_number(scores.mean_hausdorff_95),
+           "mean_assd": lv.json_number(scores.mean_assd), "mean_surface_dice": lv.json_number(scores.mean_surface_dice)}
     with open(written[1], "w") as f:
         json.dump(doc, f, indent=1)
     return written
