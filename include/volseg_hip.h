@@ -835,6 +835,29 @@ int vs_mesh_count(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int va
 int vs_mesh_emit(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int style, const void* workspace,
                  size_t workspace_bytes, float* vertices, int32_t* quads, void* stream);
 
+/* ---- the overlap table of two labellings (csrc/overlap.hip) ----
+ * a and b: the comp of vs_label_components of two volumes of the same extents (n int32 each, 0 <= a[v], b[v] < 2^31, 0 < n < 2^31,
+ * x fastest, X the row length, n a multiple of X; 4-byte aligned).  skip: n bytes or NULL; a non-zero byte leaves the voxel out.
+ * The key of a voxel is (uint64(a[v]) << 32) | uint32(b[v]).  A run starts at a voxel that is not skipped and whose key differs
+ * from that of the voxel before it in the same row; a skipped voxel before it, or x == 0, starts a run as well.
+ *
+ * vs_overlap_runs: runs[0] (one device int64, 8-byte aligned, written by the call) = the number of runs.  Every distinct key has a
+ * first voxel and that voxel starts a run, so the table below never holds more keys than this.  A memset and one launch; one
+ * 64-bit add per workgroup.
+ *
+ * vs_overlap_table: keys[s] / counts[s] (slots device uint64 / int64 each, 8-byte aligned, slots a power of two, both initialised
+ * by the call) = an open-addressing hash table of (key, voxels that have it); a free slot reads the key 0xFFFFFFFFFFFFFFFF, which
+ * no voxel has, and its count means nothing (every count starts at 1, the voxel a claim brings, so that the claim needs no add of
+ * its own: read counts only where the key is not free).  used (2 device int64, written by the call): used[0] = the occupied slots, used[1] = 1 when an
+ * insertion found no slot within `slots` probes - the call then returns VS_ERR_INVALID and vs_last_error names the table size;
+ * the table's contents are then not a table.  Insertions are one 64-bit compare-and-swap on the key and one 64-bit add on the
+ * count (none for a claim of one voxel), issued per run or per cached key of a wave, never per voxel; every probe loop ends after `slots` steps.  Integer sums:
+ * sorted by key, the occupied slots are the same bits on every run.  Two memsets and two launches (the counts' fill, the sweep), no workgroup waits on
+ * another, no host loop; the call waits for the stream before it returns, to read `used`. */
+int vs_overlap_runs(const int32_t* a, const int32_t* b, const uint8_t* skip, int64_t n, int64_t X, int64_t* runs, void* stream);
+int vs_overlap_table(const int32_t* a, const int32_t* b, const uint8_t* skip, int64_t n, int64_t X, uint64_t* keys, int64_t* counts,
+                     int64_t slots, int64_t* used, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

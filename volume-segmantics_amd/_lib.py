@@ -253,6 +253,8 @@ _SIGS = {
     "vs_mesh_workspace_bytes": (SZ, [I64, I64, I64]),
     "vs_mesh_count": (I, [P, I64, I64, I64, I, P, SZ, P, P]),
     "vs_mesh_emit": (I, [P, I64, I64, I64, I, I, P, SZ, P, P, P]),
+    "vs_overlap_runs": (I, [P, P, P, I64, I64, P, P]),
+    "vs_overlap_table": (I, [P, P, P, I64, I64, P, P, I64, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

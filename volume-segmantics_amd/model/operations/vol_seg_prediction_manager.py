@@ -142,7 +142,11 @@ class VolSeg2DPredictionManager(BaseDataManager):
         Returns the scores; ``last_evaluation`` keeps the prediction, the dropped counts and the per-slice Dice.  With the settings key
         ``evaluation_surface_distances: true`` the surface distances (utilities/surface_distance.py: Hausdorff, its 95th percentile,
         average symmetric surface distance, surface Dice at ``evaluation_surface_tolerance``, distances in ``evaluation_voxel_size``) are
-        computed as well, logged, written to ``<stem>_surface_scores.csv`` / ``.json`` and kept in ``last_evaluation["surface_scores"]``."""
+        computed as well, logged, written to ``<stem>_surface_scores.csv`` / ``.json`` and kept in ``last_evaluation["surface_scores"]``.
+        With ``evaluation_object_scores: true`` the object-level scores (utilities/object_scores.py: true and predicted connected
+        components under ``evaluation_object_connectivity`` matched at ``evaluation_object_iou``; precision, recall, F1, panoptic quality,
+        splits, merges, variation of information, adapted Rand error) are computed too, logged, written to ``<stem>_object_scores.csv``
+        / ``.json`` and ``<stem>_object_matches.csv`` and kept in ``last_evaluation["object_scores"]``."""
         from ... import dist as vdist
         from ...utilities import evaluation as ev
 
@@ -180,5 +184,10 @@ class VolSeg2DPredictionManager(BaseDataManager):
         if sd.surface_settings(self.settings)[0]:
             stem = output_path.parent / output_path.stem if output_path is not None and rank0 else None
             self.last_evaluation["surface_scores"] = sd.evaluate_surface_distances(
+                prediction, truth, classes, self.settings, label_values=values, ignore_label=ignore, device=device, stem=stem)[0]
+        from ...utilities import object_scores as obs
+        if obs.object_scores_asked(self.settings):
+            stem = output_path.parent / output_path.stem if output_path is not None and rank0 else None
+            self.last_evaluation["object_scores"] = obs.evaluate_objects(
                 prediction, truth, classes, self.settings, label_values=values, ignore_label=ignore, device=device, stem=stem)[0]
         return scores

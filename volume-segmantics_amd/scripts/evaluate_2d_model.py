@@ -9,7 +9,9 @@ an existing label volume (one the reference wrote, for instance) and also runs o
 number of distinct values over both files, class ``i`` being the ``i``-th of them in ascending order.  Both log the per-class table
 and write ``<stem>_scores.csv`` and ``<stem>_scores.json`` beside the prediction's name under ``DIR`` (``<stem>_scores_per_slice.csv``
 too with the settings key ``evaluation_per_slice: true``; ``<stem>_surface_scores.csv`` and ``<stem>_surface_scores.json`` - Hausdorff
-distances, average symmetric surface distance, surface Dice - with ``evaluation_surface_distances: true``)."""
+distances, average symmetric surface distance, surface Dice - with ``evaluation_surface_distances: true``; ``<stem>_object_scores.csv``,
+``<stem>_object_scores.json`` and ``<stem>_object_matches.csv`` - objects found, split, merged and invented, panoptic quality, variation
+of information - with ``evaluation_object_scores: true``)."""
 from __future__ import annotations
 
 import logging
@@ -46,6 +48,9 @@ def _score_existing(root, pred_path, labels_path, settings) -> None:
     if sd.surface_settings(settings)[0]:
         sd.evaluate_surface_distances(pred_classes, truth, len(values), settings, label_values=values, ignore_label=ignore,
                                       stem=root / pred_path.stem)
+    from ..utilities import object_scores as obs
+    if obs.object_scores_asked(settings):
+        obs.evaluate_objects(pred_classes, truth, len(values), settings, label_values=values, ignore_label=ignore, stem=root / pred_path.stem)
 
 
 def main(argv=None) -> None:

@@ -137,6 +137,26 @@ def wide_truth_to_classes(truth: np.ndarray, classes: int, label_values, ignore_
     return out.reshape(truth.shape)
 
 
+def class_bytes(labels, label_values, ignore_label):
+    """(uint8 volume - host array or device tensor -, 256-entry table byte -> class with 255 = ignore, 254 = no class): a uint8 volume
+    as it came with the table that maps it, a wider one mapped on the host with the identity table.  Without ``label_values`` class
+    ``i`` is the value ``i``.  What the surface distances and the object scores label their ground truth with."""
+    if lv.is_u8(labels):
+        lut = np.arange(256, dtype=np.uint8)
+        lut[254:] = INVALID
+        if label_values is not None:
+            lut = truth_table(len(label_values), label_values, None)
+        if ignore_label is not None and 0 <= int(ignore_label) <= 255:
+            lut[int(ignore_label)] = IGNORE
+        return labels, lut
+    host = lv.to_host(labels)
+    if host.dtype == np.bool_:
+        host = host.astype(np.uint8)
+    if not np.issubdtype(host.dtype, np.integer):
+        raise TypeError(f"expected an integer label volume, got {host.dtype}")
+    return wide_truth_to_classes(host, 254, label_values, ignore_label), np.arange(256, dtype=np.uint8)
+
+
 def _count_numpy(t: np.ndarray, p: np.ndarray, lut: np.ndarray, classes: int, nslabs: int):
     k2 = classes * classes
     counts = np.zeros((nslabs, classes, classes), dtype=np.int64)

@@ -134,24 +134,6 @@ def squared_distance_transform(seeds, device=None) -> np.ndarray:
     return d2.cpu().numpy().view(np.uint32).reshape(shape)
 
 
-def _class_bytes(labels, label_values, ignore_label):
-    """(uint8 volume - host array or device tensor -, 256-entry table byte -> class with 255 = ignore, 254 = no class)"""
-    if lv.is_u8(labels):
-        lut = np.arange(256, dtype=np.uint8)
-        lut[254:] = ev.INVALID
-        if label_values is not None:
-            lut = ev.truth_table(len(label_values), label_values, None)
-        if ignore_label is not None and 0 <= int(ignore_label) <= 255:
-            lut[int(ignore_label)] = ev.IGNORE
-        return labels, lut
-    host = lv.to_host(labels)
-    if host.dtype == np.bool_:
-        host = host.astype(np.uint8)
-    if not np.issubdtype(host.dtype, np.integer):
-        raise TypeError(f"expected an integer label volume, got {host.dtype}")
-    return ev.wide_truth_to_classes(host, 254, label_values, ignore_label), np.arange(256, dtype=np.uint8)
-
-
 def label_surface(labels, cls: int, *, label_values=None, ignore_label=None, device=None) -> np.ndarray:
     """uint8 mask of ``labels.shape``: 1 on the surface voxels of class ``cls``.  Class ``i`` is the value ``label_values[i]`` (default:
     ``i`` itself); voxels of ``ignore_label`` belong to no class."""
@@ -161,7 +143,7 @@ def label_surface(labels, cls: int, *, label_values=None, ignore_label=None, dev
         raise ValueError(f"class {cls}: classes are 0..253")
     shape = tuple(labels.shape)
     zyx = _zyx(shape)
-    volume, lut = _class_bytes(labels, label_values, ignore_label)
+    volume, lut = ev.class_bytes(labels, label_values, ignore_label)
     device = lv.pick_device(device, labels)
     if device is None:
         return _surface_host(lut[np.ascontiguousarray(lv.to_host(volume))] == cls).astype(np.uint8).reshape(shape)
@@ -190,7 +172,7 @@ def surface_distance_histograms(pred, truth, classes, *, label_values=None, igno
     class_list = list(range(int(classes))) if np.isscalar(classes) else [int(c) for c in classes]
     if not class_list or min(class_list) < 0 or max(class_list) > 253:
         raise ValueError(f"classes must be 0..253, got {class_list[:20]}")
-    t, lut = _class_bytes(truth, label_values, ignore_label)
+    t, lut = ev.class_bytes(truth, label_values, ignore_label)
     p = lv.lenient_u8(pred)
     device = lv.pick_device(device, pred, truth)
     full = np.zeros((len(class_list), 2, bins), dtype=np.int64)
