@@ -858,6 +858,39 @@ int vs_overlap_runs(const int32_t* a, const int32_t* b, const uint8_t* skip, int
 int vs_overlap_table(const int32_t* a, const int32_t* b, const uint8_t* skip, int64_t n, int64_t X, uint64_t* keys, int64_t* counts,
                      int64_t slots, int64_t* used, void* stream);
 
+/* ---- local thickness of a label volume (csrc/thickness.hip) ----
+ * Z x Y x X volumes, x fastest, n = Z * Y * X < 2^31 voxels and the extents vs_edt_squared takes (otherwise VS_ERR_INVALID, checked
+ * from the extents alone).  r: n uint32, the squared distance of every voxel of one label value to the nearest voxel of another
+ * value and 0 at the voxels of the other values - vs_edt_squared with seeds = (labels != value); a volume of 0xFFFFFFFF (no other
+ * value) has no centres.  The ball of v is { u in the volume : |u - v|^2 < r[v] }; T2[u] = the largest r[v] over the balls that
+ * contain u.  max_r: the largest r of the volume, 1 <= max_r < 2^32 - 1.  Maxima of integers: the same bits on every run.
+ *
+ * vs_thickness_centres: centres (capacity int32; at most one per voxel with r > 0) receives the voxel indices whose ball is not
+ * contained in the ball of one of their 26 in-volume neighbours, in no particular order: v is dropped when a neighbour n has
+ * r[n] >= need[(j - 1) * need_len + r[v]], j = 1, 2, 3 the non-zero components of n - v (a face, an edge, a corner), need = 3 rows
+ * of need_len device uint32 holding 1 + max { |p - delta|^2 : p in Z^3, |p|^2 < r }; a voxel with r[v] >= need_len is never dropped
+ * (need_len 0 and need NULL: every voxel with r > 0 is a centre).  Dropping changes no T2.  totals (2 device int64, written by the
+ * call): the centres - where it exceeds capacity the list is cut short, which the caller checks - and the rows their balls will
+ * paint: per centre the rows (dz, dy) of the bounding square of its ball that lie in the volume.  A memset and one launch.
+ *
+ * vs_thickness_paint: records the balls of centres[0 .. count) in workspace - vs_thickness_workspace_bytes(Z, Y, X, max_r) bytes:
+ * K = bit_length(min(2 h + 1, X)) levels of n uint32, h the largest integer with h^2 < max_r; 0 for arguments that do not fit -
+ * as a sparse table of range maxima: per row of a ball its x-span, of length L, is two atomic maxima on level floor(log2 L).  With
+ * zero_first != 0 the workspace is zeroed first: set it on the first call for a value; a list may be painted in several calls.
+ * largest_r: an upper bound of r over THIS call's centres (1 <= largest_r <= max_r), which sizes the grid; every r must be <=
+ * max_r.  An entry of centres outside [0, n) is skipped.  A memset and one launch; count == 0 launches nothing.
+ *
+ * vs_thickness_resolve: pushes the levels down (K - 1 streaming launches, no atomics), after which level 0 - the first n uint32
+ * of workspace - is the painted map, and writes t2[u] = that map at the voxels with labels[u] == value; the other voxels of t2
+ * are left alone, so several values share one map.  workspace, r, centres and t2 4-byte, totals 8-byte aligned. */
+size_t vs_thickness_workspace_bytes(int64_t Z, int64_t Y, int64_t X, int64_t max_r);
+int vs_thickness_centres(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const uint32_t* need, int64_t need_len, int32_t* centres,
+                         int64_t capacity, int64_t* totals, void* stream);
+int vs_thickness_paint(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const int32_t* centres, int64_t count, int64_t largest_r,
+                       int64_t max_r, void* workspace, size_t workspace_bytes, int zero_first, void* stream);
+int vs_thickness_resolve(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int64_t max_r, void* workspace,
+                         size_t workspace_bytes, uint32_t* t2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -255,6 +255,10 @@ _SIGS = {
     "vs_mesh_emit": (I, [P, I64, I64, I64, I, I, P, SZ, P, P, P]),
     "vs_overlap_runs": (I, [P, P, P, I64, I64, P, P]),
     "vs_overlap_table": (I, [P, P, P, I64, I64, P, P, I64, P, P]),
+    "vs_thickness_workspace_bytes": (SZ, [I64, I64, I64, I64]),
+    "vs_thickness_centres": (I, [P, I64, I64, I64, P, I64, P, I64, P, P]),
+    "vs_thickness_paint": (I, [P, I64, I64, I64, P, I64, I64, I64, P, SZ, I, P]),
+    "vs_thickness_resolve": (I, [P, I64, I64, I64, I, I64, P, SZ, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

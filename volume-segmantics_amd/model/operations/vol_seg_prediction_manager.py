@@ -9,7 +9,7 @@ import numpy as np
 
 from ...data.base_data_manager import BaseDataManager
 from ...utilities import base_data_utils as utils
-from ...utilities import components, measurements, meshes
+from ...utilities import components, measurements, meshes, thickness
 from .vol_seg_2d_predictor import VolSeg2dPredictor
 
 
@@ -37,7 +37,13 @@ def _write_measurements(stem, m, save):
         save(m["ids"], f"{stem}_object_ids.h5")
 
 
-# in the order they run: the measurements and the meshes are those of the volume that is saved, after any cleanup
+def _write_thickness(stem, t, save):
+    thickness.write_thickness(stem, t)
+    if t["volume"] is not None:
+        save(t["volume"], f"{stem}_thickness.h5")
+
+
+# in the order they run: the measurements, the meshes and the thickness are those of the volume that is saved, after any cleanup
 LABEL_STEPS = (
     LabelStep("clean", lambda s: any(getattr(s, key, None) for key in ("postprocess_min_object_size", "postprocess_keep_largest", "postprocess_fill_holes")),
               "there are no components to clean (unset the postprocess_* keys or set one_hot: False)", _clean,
@@ -53,6 +59,11 @@ LABEL_STEPS = (
               lambda volume, s, device: (volume, meshes.mesh_label_volume(volume, s, device=device)),
               lambda m: "Surface meshes of the label volume:\n" + meshes.mesh_summary_text(m["summary"]),
               "last_meshes", lambda stem, m, save: meshes.write_meshes(stem, m)),
+    LabelStep("thickness", lambda s: bool(getattr(s, "thickness_map", False)),
+              "there is no material to measure the thickness of (unset thickness_map or set one_hot: False)",
+              lambda volume, s, device: (volume, thickness.thickness_label_volume(volume, s, device=device)),
+              lambda t: "Local thickness of the label volume:\n" + thickness.thickness_summary_text(t),
+              "last_thickness", _write_thickness),
 )
 
 
@@ -79,7 +90,12 @@ class VolSeg2DPredictionManager(BaseDataManager):
         With ``mesh_surfaces: true`` the same volume is meshed (utilities/meshes.py: per value of ``mesh_values`` a closed surface net in
         ``mesh_style``, physical units from ``mesh_voxel_size``): the summary is logged, ``last_meshes`` keeps the arrays and the figures,
         and ``<stem>_mesh_<value>.ply`` / ``.stl`` (``mesh_format``, ``mesh_triangulate``) and ``<stem>_meshes.json`` are written beside the
-        label volume."""
+        label volume.
+        With ``thickness_map: true`` the same volume gets its local thickness (utilities/thickness.py: per value of ``thickness_values`` the
+        diameter of the largest ball inside the material that contains the voxel, physical units from ``thickness_voxel_size``, the
+        work bounded by ``thickness_max_work``): the per-value figures are logged, ``last_thickness`` keeps the squared map, the histograms
+        and the figures, and ``<stem>_thickness.json`` / ``.csv`` - with ``thickness_save_volume`` also ``<stem>_thickness.h5``, the float32
+        thicknesses - are written beside the label volume."""
         one_hot = self.settings.one_hot
         steps = [step for step in LABEL_STEPS if step.asked(self.settings)]
         if one_hot and steps:

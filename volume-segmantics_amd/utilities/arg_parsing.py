@@ -1,6 +1,6 @@
 """Command lines of the commands (scripts/train_2d_model.py, scripts/predict_2d_model.py, scripts/evaluate_2d_model.py,
-scripts/clean_2d_prediction.py, scripts/measure_2d_prediction.py, scripts/mesh_2d_prediction.py); the first two take the reference's
-arguments:
+scripts/clean_2d_prediction.py, scripts/measure_2d_prediction.py, scripts/mesh_2d_prediction.py, scripts/thickness_2d_prediction.py);
+the first two take the reference's arguments:
 
     train:    --data FILE [FILE ...] --labels FILE [FILE ...] [--data_dir DIR]
     predict:  MODEL FILE [--data_dir DIR]
@@ -8,6 +8,7 @@ arguments:
     clean:    PRED [--data_dir DIR] [--output OUT]
     measure:  PRED [--data_dir DIR] [--output STEM]
     mesh:     PRED [--data_dir DIR] [--output STEM]
+    thickness: PRED [--data_dir DIR] [--output STEM]
 
 ``--data_dir`` (default: the working directory) holds ``volseg-settings/`` and receives every output.  A volume or model file
 with a suffix the engine does not read, or one that does not exist, is a usage error (argparse: exit status 2)."""
@@ -123,6 +124,15 @@ def get_2d_meshing_parser() -> argparse.ArgumentParser:
                                 "the files written are STEM_mesh_<value>.ply / .stl and STEM_meshes.json (default: <stem of PRED> under the data directory)")
 
 
+def get_2d_thickness_parser() -> argparse.ArgumentParser:
+    """PRED [--data_dir DIR] [--output STEM]: the local thickness of an existing label volume with the thickness_* keys of the predict settings."""
+    return _label_volume_parser("Local thickness of a label volume: per label value, for every voxel the diameter of the largest "
+                                "ball inside the material that contains it (thickness_* settings keys).",
+                                "the label volume to measure", "STEM",
+                                "the files written are STEM_thickness.csv, STEM_thickness.json and, with thickness_save_volume, STEM_thickness.h5 "
+                                "(default: <stem of PRED> under the data directory)")
+
+
 def parse_cleaning_args(argv=None) -> argparse.Namespace:
     """The clean command's arguments; an --output with a suffix the engine does not write is a usage error (exit 2)."""
     parser = get_2d_cleaning_parser()
@@ -147,6 +157,11 @@ def parse_measuring_args(argv=None) -> argparse.Namespace:
 def parse_meshing_args(argv=None) -> argparse.Namespace:
     """The mesh command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
     return _parse_stem_args(get_2d_meshing_parser(), argv)
+
+
+def parse_thickness_args(argv=None) -> argparse.Namespace:
+    """The thickness command's arguments; an --output whose directory does not exist is a usage error (exit 2)."""
+    return _parse_stem_args(get_2d_thickness_parser(), argv)
 
 
 def open_label_volume(parse, argv) -> argparse.Namespace:

@@ -149,3 +149,16 @@ def json_number(x):
     """a float for a JSON document: NaN is written as null, infinity as the string "inf" """
     x = float(x)
     return None if np.isnan(x) else "inf" if np.isinf(x) else x
+
+
+def percentile_from_counts(values: np.ndarray, counts: np.ndarray, q: float) -> float:
+    """NumPy's default (linear) percentile of the multiset that holds values[i] counts[i] times; values ascending"""
+    total = int(counts.sum())
+    cum = np.cumsum(counts)
+    virtual = (total - 1) * (q / 100.0)
+    lo = int(np.floor(virtual))
+    hi = min(lo + 1, total - 1)
+    t = virtual - lo
+    a = float(values[np.searchsorted(cum, lo, side="right")])
+    b = float(values[np.searchsorted(cum, hi, side="right")])
+    return a + (b - a) * t if t < 0.5 else b - (b - a) * (1.0 - t)

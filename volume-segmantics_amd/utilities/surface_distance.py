@@ -89,7 +89,9 @@ def _histogram_host(surface: np.ndarray, d2: np.ndarray, bins: int) -> np.ndarra
 
 
 # ---- device routes ---------------------------------------------------------------------------------------------------------------
-def _edt_device(seeds_dev, zyx, d2_dev, workspace):
+def edt_device(seeds_dev, zyx, d2_dev, workspace):
+    """vs_edt_squared on resident memory: ``seeds_dev`` n aligned uint8, ``d2_dev`` n int32 (uint32 bits), ``workspace`` a uint8 tensor of
+    ``vs_edt_workspace_bytes`` bytes (empty where none is needed)"""
     import torch
     from .. import _lib
     with torch.cuda.device(seeds_dev.device):
@@ -130,7 +132,7 @@ def squared_distance_transform(seeds, device=None) -> np.ndarray:
         s = (s != 0).to(torch.uint8)
     s = lv.aligned_u8(s, device)
     d2 = torch.empty(n, dtype=torch.int32, device=device)
-    _edt_device(s, zyx, d2, _workspace(zyx, device))
+    edt_device(s, zyx, d2, _workspace(zyx, device))
     return d2.cpu().numpy().view(np.uint32).reshape(shape)
 
 
@@ -210,7 +212,7 @@ def surface_distance_histograms(pred, truth, classes, *, label_values=None, igno
                 _surface_device(td, lut_dev, c, zyx, masks[0], counts[0:1])
                 _surface_device(pd, None, c, zyx, masks[1], counts[1:2])
                 for direction in range(2):
-                    _edt_device(masks[1 - direction], zyx, d2, workspace)
+                    edt_device(masks[1 - direction], zyx, d2, workspace)
                     _lib.check(_lib.lib.vs_surface_distance_histogram(_lib.ptr(masks[direction]), _lib.ptr(d2), n, bins, _lib.ptr(hist),
                                                                       _lib.stream_ptr()))
                     full[i, direction] = hist.cpu().numpy()
@@ -258,19 +260,6 @@ class SurfaceScores:
         return int(len(self.hausdorff))
 
 
-def _percentile_from_counts(values: np.ndarray, counts: np.ndarray, q: float) -> float:
-    """NumPy's default (linear) percentile of the multiset that holds values[i] counts[i] times; values ascending"""
-    total = int(counts.sum())
-    cum = np.cumsum(counts)
-    virtual = (total - 1) * (q / 100.0)
-    lo = int(np.floor(virtual))
-    hi = min(lo + 1, total - 1)
-    t = virtual - lo
-    a = float(values[np.searchsorted(cum, lo, side="right")])
-    b = float(values[np.searchsorted(cum, hi, side="right")])
-    return a + (b - a) * t if t < 0.5 else b - (b - a) * (1.0 - t)
-
-
 def surface_scores_from_histograms(hists, inf_counts, tolerance: float = 1.0, voxel_size: float = 1.0) -> SurfaceScores:
     """The figures of ``surface_distance_histograms``' output.  A class absent from both volumes has NaN for every figure and is left
     out of the means; a class present in only one has every distance figure ``inf`` and surface Dice 0."""
@@ -296,7 +285,7 @@ def surface_scores_from_histograms(hists, inf_counts, tolerance: float = 1.0, vo
         pooled = h[i, 0] + h[i, 1]
         used = np.flatnonzero(pooled)
         figures["hausdorff"][i] = dist[used[-1]]
-        figures["hausdorff_95"][i] = _percentile_from_counts(dist[used], pooled[used], 95.0)
+        figures["hausdorff_95"][i] = lv.percentile_from_counts(dist[used], pooled[used], 95.0)
         figures["assd"][i] = float((pooled[used] * dist[used]).sum()) / (na + nb)
         figures["t2p"][i] = float((h[i, 0, used] * dist[used]).sum()) / na
         figures["p2t"][i] = float((h[i, 1, used] * dist[used]).sum()) / nb
