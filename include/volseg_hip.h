@@ -157,6 +157,27 @@ int vs_bn_bwd_recompute(int dtype, const void* dy, const void* y, const void* x,
 /* eval-mode folding: scale = gamma / sqrt(var + eps), shift = beta - mean * scale */
 int vs_bn_fold(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
                float eps, float* scale, float* shift, int c, void* stream);
+/* Test seams: the one-launch BatchNorm sweeps that the network's plan runs behind a convolution whose epilogue already summed the
+ * statistics, on sums the caller wrote.  No reference counterpart: tests and tooling.
+ *  vs_bn_apply_from_partials: partial = [nparts][2][c] fp32 rows of per-channel (sum x, sum x^2), 16-byte aligned.  Every workgroup sums
+ *    them in fp64 and normalises its rows; workgroup 0 writes mean / invstd and takes one momentum step on the running statistics.
+ *  vs_bn_apply_from_bins: the same from [nb][2][c] signed 64-bit fixed-point bins (sum x * vs_stat_scale(0), sum x^2 * vs_stat_scale(1));
+ *    stat_rows > 0: the sums describe that many rows (cross-rank statistics), 0 = rows.
+ *  vs_bn_bwd_from_partials: g is the gradient already masked by the ReLU, partial = [nparts][2][c] rows of (sum g, sum g * xhat).  Few
+ *    rows (option "bn_inline_rows") and c in 8 .. 512 with 256 % (c / 2) == 0: summed inside the apply sweep; otherwise a finalise
+ *    launch and the plain apply sweep.  dres (optional) = g.
+ *  vs_bn_finalize_partials: mean / invstd / running statistics alone from the rows of vs_bn_apply_from_partials. */
+int vs_bn_apply_from_partials(int dtype, const void* x, const float* partial, int nparts, float eps, float momentum, float* mean,
+                              float* invstd, float* running_mean, float* running_var, const float* gamma, const float* beta,
+                              const void* residual, int relu, void* y, int64_t rows, int c, void* stream);
+int vs_bn_apply_from_bins(int dtype, const void* x, const void* bins, int nb, float eps, float momentum, float* mean, float* invstd,
+                          float* running_mean, float* running_var, const float* gamma, const float* beta, const void* residual,
+                          int relu, void* y, int64_t rows, int c, int64_t stat_rows, void* stream);
+int vs_bn_bwd_from_partials(int dtype, const void* g, const void* x, const float* mean, const float* invstd, const float* gamma,
+                            void* dx, void* dres, float* dgamma, float* dbeta, int64_t rows, int c, const float* partial, int nparts,
+                            void* stream);
+int vs_bn_finalize_partials(const float* partial, int nparts, int c, int64_t rows, float eps, float momentum, float* mean,
+                            float* invstd, float* running_mean, float* running_var, void* stream);
 
 /* MaxPool2d(3, stride 2, pad 1) on NHWC; idx: uint8 [n][h/2][w/2][c] window position of the first max. */
 int vs_maxpool_fwd(int dtype, const void* x, void* y, uint8_t* idx, int n, int h, int w, int c, void* stream);

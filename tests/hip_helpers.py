@@ -44,6 +44,22 @@ def sync():
     torch.cuda.synchronize()
 
 
+class option:
+    """set runtime options through vs_set_option for a block, and put back what vs_get_option returned before it"""
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        L = lib()
+        self.old = {k: L.lib.vs_get_option(k.encode()) for k in self.kv}
+        for k, v in self.kv.items():
+            L.set_option(k, v)
+
+    def __exit__(self, *exc):
+        for k, v in self.old.items():
+            lib().set_option(k, v)
+
+
 def conv_desc(L, code, n, hin, win, c0, cout, k, stride, pad, c1=0, up0=0, relu=0, out_f32=0, split_c=0, groups=0, dilation=0):
     return L.ConvDesc(dtype=code, n=n, hin=hin, win=win, c0=c0, c1=c1, up0=up0, cout=cout, kh=k, kw=k,
                       stride=stride, pad=pad, relu=relu, out_f32=out_f32, split_c=split_c, groups=groups, dilation=dilation)

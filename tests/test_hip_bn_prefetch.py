@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from hip_helpers import DEV, lib, rounded, sync, tdtype, tol
+from hip_helpers import option as _option
 
 pytestmark = pytest.mark.gpu
 CODES = [0, 1]
@@ -18,21 +19,6 @@ CODES = [0, 1]
 # multi-block case; rpb = 5 with 16 idle threads, several blocks and a ragged tail; rpb = 1
 SHAPES = [(1, 8), (37, 24), (1000, 64), (4100, 384), (130, 2048)]
 REF_SHAPE = (1000, 64)
-
-
-class _option:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        L = lib()
-        self.old = {k: L.lib.vs_get_option(k.encode()) for k in self.kv}
-        for k, v in self.kv.items():
-            L.set_option(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            lib().set_option(k, v)
 
 
 @functools.lru_cache(maxsize=None)

@@ -716,7 +716,16 @@ def test_batchnorm_train_fwd_bwd(code, c, rows_shape):
     t = tol(code, x.grad.abs().max().item())
     assert torch.allclose(from_nhwc(dres), res.grad, **tol(code, res.grad.abs().max().item()))
     assert torch.allclose(dbeta.cpu(), beta.grad, rtol=1e-3, atol=1e-3 * beta.grad.abs().max().item())
-    assert torch.allclose(dgamma.cpu(), gamma.grad, rtol=2e-3, atol=2e-3 * gamma.grad.abs().max().item() + (0 if code == 0 else 0.05))
+    # dgamma: the float64 sum of g xhat under the device's mean / invstd, within the bound derived from the sweep's summation structure
+    # (tests/batchnorm_cases.py bwd_sums_figures: a few 1e-6 of sum |g xhat| on these shapes, no absolute slack for either dtype) - tighter on
+    # every one of these shapes than the rtol 2e-3, atol 2e-3 max|dgamma| (+ 0.05 under bf16) against float32 torch that stood here
+    import batchnorm_cases as B
+    flat = lambda v: v.detach().permute(0, 2, 3, 1).reshape(rows, c)
+    gm = flat(dy).double() * (flat(y) > 0)
+    figures = B.bwd_sums_figures("bwd", gm, flat(x), mean.cpu(), invstd.cpu(), dgamma.cpu(), dbeta.cpu(), B.rowmap(rows, c))
+    assert all(ratio <= 1.0 for _, ratio in figures), figures
+    bound = B.sum_factor(B.rowmap(rows, c)) * (gm * (flat(x).double() - mean.cpu().double()) * invstd.cpu().double()).abs().sum(0) + B.U * gamma.grad.abs()
+    assert (bound <= 2e-3 * gamma.grad.abs() + 2e-3 * gamma.grad.abs().max()).all()      # (the comparison that justifies the replacement)
     assert torch.allclose(from_nhwc(dx), x.grad, **t)
 
 

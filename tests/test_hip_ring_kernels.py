@@ -49,13 +49,37 @@ def _assert_ring(L, d, t, code):
     assert got == code, f"this launch selects kernel variant {got}, not the ring kernel {code} the batch-32 step runs"
 
 
-@pytest.mark.parametrize("case", FWD_CASES)
+# the two smallest cases once more with outputs of non-zero mean (|mean| / std from about 0 to 28 and to 19 across the output channels)
+NONZERO_MEAN = ("layer4-512to512@8-mode3", "layer3-256to256@16-mode2")
+FWD_STAT_CASES = ([pytest.param(p.values[0], False, id=p.id) for p in FWD_CASES] +
+                  [pytest.param(p.values[0], True, id=p.id + "-nonzero-mean") for p in FWD_CASES if p.id in NONZERO_MEAN])
+
+
+def _nonzero_mean_statistics(case, stats):
+    """|randn| input and a constant added to the centre-tap weights of each output channel (tests/batchnorm_cases.py ring_inputs): the
+    variance from the bins / partial rows within the bound derived there from conv_epilogue, which grows like 1 + rho^2; the bins then
+    feed vs_bn_apply_from_bins, y against the float64 BatchNorm of the float64 convolution of the same bf16 operands."""
+    import batchnorm_cases as B
+    h, w, c0, c1, up0, cout, code = case
+    figures, curve = B.ring_nonzero_mean_figures(h, c0, cout, stats, code, N)
+    assert curve[:, 0].min() < 2 and curve[:, 0].max() > 16, (curve[:, 0].min(), curve[:, 0].max())      # the range of rho this launch covers
+    failed = []
+    for label, ratio in figures:
+        print(f"{stats} {label}: {ratio:.3g} of the bound")
+        if not ratio <= 1.0:
+            failed.append((label, ratio))
+    assert not failed, failed
+
+
+@pytest.mark.parametrize("case,nonzero_mean", FWD_STAT_CASES)
 @pytest.mark.parametrize("stats", ["bins", "rows"])
-def test_ring_forward_with_batch_statistics(case, stats):
+def test_ring_forward_with_batch_statistics(case, nonzero_mean, stats):
     """Training forward: z = conv(x, w) stored bf16, and the per-channel sum / sum of squares of the fp32 accumulators (what
     F.batch_norm(training=True) reduces) from the epilogue - as 64-bit fixed-point bins (the default of the step) and as fp32 partial
     rows.  Against F.conv2d on the same bf16-rounded operands."""
     L = lib()
+    if nonzero_mean:
+        return _nonzero_mean_statistics(case, stats)
     h, w, c0, c1, up0, cout, code = case
     g = torch.Generator().manual_seed(31)
     x0, x1, xin, wt = _inputs(g, h, w, c0, c1, up0, cout)

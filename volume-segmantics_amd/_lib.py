@@ -156,6 +156,10 @@ _SIGS = {
     "vs_bn_bwd": (I, [I, P, P, P, P, P, P, I, P, P, P, P, I64, I, P, SZ, P]),
     "vs_bn_bwd_recompute": (I, [I, P, P, P, P, P, P, P, I, P, P, P, P, I64, I, P, SZ, P]),
     "vs_bn_fold": (I, [P, P, P, P, F, P, P, I, P]),
+    "vs_bn_apply_from_partials": (I, [I, P, P, I, F, F, P, P, P, P, P, P, P, I, P, I64, I, P]),
+    "vs_bn_apply_from_bins": (I, [I, P, P, I, F, F, P, P, P, P, P, P, P, I, P, I64, I, I64, P]),
+    "vs_bn_bwd_from_partials": (I, [I, P, P, P, P, P, P, P, P, P, I64, I, P, I, P]),
+    "vs_bn_finalize_partials": (I, [P, I, I, I64, F, F, P, P, P, P, P]),
     "vs_maxpool_fwd": (I, [I, P, P, P, I, I, I, I, P]),
     "vs_maxpool_bwd": (I, [I, P, P, P, I, I, I, I, I, P]),
     "vs_upsample2x_bwd": (I, [I, P, P, I, I, I, I, P]),

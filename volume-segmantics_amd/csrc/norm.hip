@@ -541,6 +541,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize(const float* __restrict__
 // bn_bwd_finalize forms); workgroup 0 publishes dgamma / dbeta.  One launch and one dependent phase fewer per unit.
 // BINS (with INLINE): `partial` holds nparts rows of 64-bit fixed-point bins ([row][2][c], sums scaled by kBwdStatScale, added
 // atomically by the dgrad epilogue that completed the gradient - ConvParams::bstats_bins): integer sums, any order, same bits.
+// (BINS = true is instantiated by no launch in this library and run by no test: no dgrad epilogue fills such bins today.)
 // PF: the first trip's rows (dy, x, y) and mean / invstd / gamma / beta are loaded before the prologue (INLINE: the partial-row or bin
 // sum; otherwise the dbeta / dgamma loads and their products), and the `relu` test sits outside the row loop
 template <typename T, bool RECOMPUTE, bool INLINE = false, bool BINS = false, bool PF = false>
@@ -964,4 +965,40 @@ extern "C" int vs_bn_fold(const float* gamma, const float* beta, const float* ru
                        running_var, eps, scale, shift, c);
     VS_LAUNCH_CHECK();
     return VS_OK;
+}
+
+// ---- test seams: the inline sweeps and the partial-row finalise on rows the caller wrote (no kernel or launch function of their own;
+// the network's plan reaches the same launch functions with the rows its convolution epilogues left)
+extern "C" int vs_bn_apply_from_partials(int dtype, const void* x, const float* partial, int nparts, float eps, float momentum, float* mean,
+                                         float* invstd, float* running_mean, float* running_var, const float* gamma, const float* beta,
+                                         const void* residual, int relu, void* y, int64_t rows, int c, void* stream) {
+    VS_REQUIRE(x && partial && mean && invstd && gamma && beta && y, "bn_apply_from_partials: null pointer");
+    VS_REQUIRE(nparts >= 1 && rows >= 1 && (running_mean == nullptr) == (running_var == nullptr), "bn_apply_from_partials: bad row counts or running statistics");
+    return launch_bn_apply_from_partials(dtype, x, partial, nparts, eps, momentum, mean, invstd, running_mean, running_var, gamma, beta, residual,
+                                         relu, y, rows, c, (hipStream_t)stream);
+}
+
+extern "C" int vs_bn_apply_from_bins(int dtype, const void* x, const void* bins, int nb, float eps, float momentum, float* mean, float* invstd,
+                                     float* running_mean, float* running_var, const float* gamma, const float* beta, const void* residual,
+                                     int relu, void* y, int64_t rows, int c, int64_t stat_rows, void* stream) {
+    VS_REQUIRE(x && bins && mean && invstd && gamma && beta && y, "bn_apply_from_bins: null pointer");
+    VS_REQUIRE(nb >= 1 && rows >= 1 && stat_rows >= 0 && (running_mean == nullptr) == (running_var == nullptr), "bn_apply_from_bins: bad row counts or running statistics");
+    return launch_bn_apply_from_bins(dtype, x, (const unsigned long long*)bins, nb, eps, momentum, mean, invstd, running_mean, running_var, gamma,
+                                     beta, residual, relu, y, rows, c, (hipStream_t)stream, stat_rows);
+}
+
+extern "C" int vs_bn_bwd_from_partials(int dtype, const void* g, const void* x, const float* mean, const float* invstd, const float* gamma,
+                                       void* dx, void* dres, float* dgamma, float* dbeta, int64_t rows, int c, const float* partial,
+                                       int nparts, void* stream) {
+    VS_REQUIRE(g && x && mean && invstd && gamma && dx && dgamma && dbeta && partial, "bn_bwd_from_partials: null pointer");
+    VS_REQUIRE(nparts >= 1 && rows >= 1, "bn_bwd_from_partials: bad row counts");
+    return launch_bn_bwd_from_partials(dtype, g, x, mean, invstd, gamma, dx, dres, dgamma, dbeta, rows, c, partial, nparts, (hipStream_t)stream,
+                                       nullptr);
+}
+
+extern "C" int vs_bn_finalize_partials(const float* partial, int nparts, int c, int64_t rows, float eps, float momentum, float* mean,
+                                       float* invstd, float* running_mean, float* running_var, void* stream) {
+    VS_REQUIRE(partial && mean && invstd, "bn_finalize_partials: null pointer");
+    VS_REQUIRE(nparts >= 1 && c >= 1 && rows >= 1 && (running_mean == nullptr) == (running_var == nullptr), "bn_finalize_partials: bad counts or running statistics");
+    return launch_bn_finalize_partials(partial, nparts, c, rows, eps, momentum, mean, invstd, running_mean, running_var, (hipStream_t)stream);
 }
