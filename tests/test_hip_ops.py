@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as CC
 from hip_helpers import (DEV, conv_desc, from_nhwc, lib, rounded, sync, tdtype, to_nhwc, tol, w_krsc)
 
 pytestmark = pytest.mark.gpu
@@ -38,6 +39,11 @@ def _conv_case(code, n, h, w, cin, cout, k, stride, pad, seed=0, relu=0, affine=
     got = from_nhwc(y)
     assert torch.isfinite(got).all()
     assert torch.allclose(got, ref, **tol(code, ref.abs().max().item())), (got - ref).abs().max()
+    # and within the per-element bound of tests/conv_cases.py, against the float64 convolution of the same operands
+    ref64, bound = CC.reference_and_bound(code, x, None, wt, stride=stride, pad=pad, scale=scale, shift=shift, residual=res, relu=int(bool(relu)))
+    fig = CC.figure_against(got, ref64, bound)
+    print(f"conv {CC.DT[code]} {(n, h, w, cin, cout, k, stride, pad)} relu={int(bool(relu))} affine={affine} residual={residual}: {fig:.3g} of the bound")
+    assert fig <= 1.0, fig
 
 
 @pytest.mark.parametrize("code", CODES)

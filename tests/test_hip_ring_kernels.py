@@ -8,11 +8,13 @@ epilogue, the split + 2x2-pooled data gradient of a decoder concatenation, the z
 gradient, and normalise-on-load.  Reference call sites: the model's forward and loss.backward() of _train_one_batch
 (volume_segmantics/model/operations/vol_seg_2d_trainer.py:424, 429)."""
 import ctypes as C
+import functools
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as CC
 from hip_helpers import DEV, conv_desc, from_nhwc, lib, rounded, sync, to_nhwc, tol, w_krsc
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +44,14 @@ def _inputs(g, h, w, c0, c1, up0, cout):
         xin = torch.cat([xin, x1], 1)
     wt = rounded(torch.randn(cout, c0 + c1, 3, 3, generator=g) / ((c0 + c1) * 9) ** 0.5, BF)
     return x0, x1, xin, wt
+
+
+@functools.lru_cache(maxsize=8)
+def _forward_reference_and_bound(case):
+    """float64 convolution of test_ring_forward_with_batch_statistics' operands and its per-element bound, once for both statistics forms"""
+    h, w, c0, c1, up0, cout, code = case
+    x0, x1, _, wt = _inputs(torch.Generator().manual_seed(31), h, w, c0, c1, up0, cout)
+    return CC.reference_and_bound(BF, x0, x1, wt, up0=up0, pad=1)
 
 
 def _assert_ring(L, d, t, code):
@@ -103,6 +113,9 @@ def test_ring_forward_with_batch_statistics(case, nonzero_mean, stats):
     got = from_nhwc(y)
     assert torch.isfinite(got).all()
     assert torch.allclose(got, ref, **tol(BF, ref.abs().max().item())), (got - ref).abs().max()
+    fig = CC.figure_against(got, *_forward_reference_and_bound(case))       # the per-element bound of tests/conv_cases.py
+    print(f"ring forward {case}: {fig:.3g} of the bound")
+    assert fig <= 1.0, fig
     if stats == "bins":
         tot = bins.sum(0).cpu().double()
         s1, s2 = tot[0] / L.lib.vs_stat_scale(0), tot[1] / L.lib.vs_stat_scale(1)
