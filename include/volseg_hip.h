@@ -615,6 +615,33 @@ int vs_mean_iou(const float* input, const void* targets, int target_is_f32, int 
  * column (torch.nn.functional.one_hot would raise). */
 int vs_onehot_u8(const uint8_t* labels, int n, int classes, int64_t hw, uint8_t* onehot, void* stream);
 
+/* Sparse labels: training on volumes in which only some voxels carry a label (the settings key `ignore_label`).
+ * valid (n, h*w) uint8 is 1 where the pixel is labelled.  vs_onehot_valid_u8 writes vs_onehot_u8's bytes and, in the same
+ * sweep, valid = (labels != ignore).  The *_masked entry points are the calls above with every sum over pixels restricted to the
+ * valid ones: with M = sum valid, the BCE term is sum / (M K), the cross entropy sum / M, the complementary channel of the
+ * one-class generalised Dice uses M; M is counted on the device, in integers.  Gradients are written as exactly 0 at ignored
+ * pixels.  M = 0: BCE and cross-entropy terms are 0, the Dice terms follow their formulas (loss 1), every gradient is 0, nothing
+ * is NaN.  With valid all ones the results equal the unmasked calls bit for bit.  (One-class generalised Dice: once a pixel is
+ * ignored, the gradient of a foreground pixel comes from a coefficient of its own instead of the sum of two fp32 coefficients
+ * that cancel where every valid pixel is foreground.)  A mask pointer that is not 4-byte aligned
+ * takes the scalar kernels.  vs_mean_iou_masked counts intersection and union over valid pixels only and leaves a sample without
+ * a valid pixel out of the mean over samples (NaN when no sample is left).  Workspaces: vs_dice_workspace as above;
+ * vs_seg_loss_masked_workspace and vs_mean_iou_masked_workspace are larger than the unmasked ones by the valid-pixel counts. */
+int vs_onehot_valid_u8(const uint8_t* labels, int n, int classes, int64_t hw, int ignore, uint8_t* onehot, uint8_t* valid, void* stream);
+int vs_dice_loss_fwd_masked(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n, int classes,
+                            int64_t hw, float eps, float* loss, float* workspace, size_t workspace_bytes, void* stream);
+int vs_dice_loss_bwd_masked(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, const float* grad_out,
+                            int n, int classes, int64_t hw, float eps, const float* workspace, float* dlogits, void* stream);
+size_t vs_seg_loss_masked_workspace(int classes);
+int vs_seg_loss_fwd_masked(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n,
+                           int classes, int64_t hw, float alpha, float beta, float eps, float* loss, float* workspace,
+                           size_t workspace_bytes, void* stream);
+int vs_seg_loss_bwd_masked(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                           const float* grad_out, int n, int classes, int64_t hw, const float* workspace, float* dlogits, void* stream);
+size_t vs_mean_iou_masked_workspace(int n, int classes);
+int vs_mean_iou_masked(const float* input, const void* targets, int target_is_f32, const uint8_t* valid, int from_logits, int n,
+                       int classes, int64_t hw, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training augmentations on the device (get_train_augs, data/augmentations.py:68-101; applied per sample by the reference's
  * DataLoader workers, data/datasets.py:42-60)

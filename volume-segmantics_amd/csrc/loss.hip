@@ -14,9 +14,14 @@ constexpr int kBlocks = 512;
 
 template <typename TT> __device__ __forceinline__ float tval(const TT* t, size_t i) { return (float)t[i]; }
 
-template <typename TT>
-__global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restrict__ x, const TT* __restrict__ t, int n, int k,
-                                                         int64_t hw, float* __restrict__ partial) {
+// MASKED (every kernel of this file that carries the flag): `valid` (n, hw) uint8 is 1 where the pixel is labelled; a pixel with
+// valid == 0 adds nothing to any sum and gets a gradient of exactly 0.  Values are selected, never multiplied, so a NaN logit
+// under an ignored pixel stays out of the sums, and an all-ones mask leaves every operation and its order as in the unmasked
+// instantiation, which is the code without the flag.
+template <typename TT, bool MASKED>
+__global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restrict__ x, const TT* __restrict__ t,
+                                                         const uint8_t* __restrict__ valid, int n, int k, int64_t hw,
+                                                         float* __restrict__ partial) {
     __shared__ float red[3][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int c = 0; c < k; ++c) {
@@ -24,6 +29,7 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
         for (int b = 0; b < n; ++b) {
             const size_t base = ((size_t)b * k + c) * hw;
             for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
+                if constexpr (MASKED) { if (!valid[(size_t)b * hw + i]) continue; }
                 const float xv = x[base + i], tv = tval(t, base + i);
                 si += xv * tv; sx += xv * xv; st += tv * tv;
             }
@@ -47,9 +53,13 @@ template <> struct TV4<uint8_t> {
     typedef uchar4 type;
     static __device__ __forceinline__ float4 f(uchar4 v) { return make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w); }
 };
-template <typename TT>
-__global__ __launch_bounds__(256) void dice_partial4_kernel(const float* __restrict__ x, const TT* __restrict__ t, int n, int k,
-                                                          int64_t hw, float* __restrict__ partial) {
+__device__ __forceinline__ float4 keep4(float4 v, uchar4 m) {
+    return make_float4(m.x ? v.x : 0.f, m.y ? v.y : 0.f, m.z ? v.z : 0.f, m.w ? v.w : 0.f);
+}
+template <typename TT, bool MASKED>
+__global__ __launch_bounds__(256) void dice_partial4_kernel(const float* __restrict__ x, const TT* __restrict__ t,
+                                                          const uint8_t* __restrict__ valid, int n, int k, int64_t hw,
+                                                          float* __restrict__ partial) {
     __shared__ float red[3][4];
     typedef typename TV4<TT>::type TQ;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -66,6 +76,10 @@ __global__ __launch_bounds__(256) void dice_partial4_kernel(const float* __restr
                 const size_t at = ((size_t)b * k + c) * hw + (size_t)i * 4;
                 xv[u] = ok ? *reinterpret_cast<const float4*>(x + at) : make_float4(0.f, 0.f, 0.f, 0.f);
                 tv[u] = ok ? TV4<TT>::f(*reinterpret_cast<const TQ*>(t + at)) : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (MASKED) {
+                    const uchar4 m = ok ? *reinterpret_cast<const uchar4*>(valid + (size_t)b * hw + (size_t)i * 4) : make_uchar4(0, 0, 0, 0);
+                    xv[u] = keep4(xv[u], m); tv[u] = keep4(tv[u], m);
+                }
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -104,14 +118,19 @@ __global__ __launch_bounds__(64) void dice_finalize_kernel(const float* __restri
     if (lane == 0) *loss = (float)(1.0 - acc / k);
 }
 
-template <typename TT>
+template <typename TT, bool MASKED>
 __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict__ x, const TT* __restrict__ t,
-                                                      const float* __restrict__ stats, const float* __restrict__ gout,
-                                                      float eps, int n, int k, int64_t hw, float* __restrict__ dx) {
+                                                      const uint8_t* __restrict__ valid, const float* __restrict__ stats,
+                                                      const float* __restrict__ gout, float eps, int n, int k, int64_t hw,
+                                                      float* __restrict__ dx) {
     const int64_t total = (int64_t)n * k * hw;
     const float g = (gout ? *gout : 1.f) * (-2.f / (float)k);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)((i / hw) % k);
+        const int64_t plane = i / hw;
+        const int c = (int)(plane % k);
+        if constexpr (MASKED) {
+            if (!valid[(size_t)(plane / k) * hw + (i - plane * hw)]) { dx[i] = 0.f; continue; }
+        }
         const float I = stats[2 * c], D = stats[2 * c + 1];
         const float xv = x[i], tv = tval(t, i);
         dx[i] = D > eps ? g * (tv * D - 2.f * xv * I) / (D * D) : g * tv / eps;
@@ -120,15 +139,17 @@ __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict_
 
 
 // 16 bytes per lane, two vectors in flight (hw % 4 == 0: a vector never straddles two class planes)
-template <typename TT>
+template <typename TT, bool MASKED>
 __global__ __launch_bounds__(256) void dice_grad4_kernel(const float* __restrict__ x, const TT* __restrict__ t,
-                                                       const float* __restrict__ stats, const float* __restrict__ gout,
-                                                       float eps, int n, int k, int64_t hw, float* __restrict__ dx) {
+                                                       const uint8_t* __restrict__ valid, const float* __restrict__ stats,
+                                                       const float* __restrict__ gout, float eps, int n, int k, int64_t hw,
+                                                       float* __restrict__ dx) {
     typedef typename TV4<TT>::type TQ;
     const int64_t nv = hw >> 2, total = (int64_t)n * k * nv, stride = (int64_t)gridDim.x * 256;
     const float g = (gout ? *gout : 1.f) * (-2.f / (float)k);
     for (int64_t v0 = (int64_t)blockIdx.x * 256 + threadIdx.x; v0 < total; v0 += 2 * stride) {
         float4 xv[2], tv[2];
+        uchar4 mv[2];
         bool ok[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -136,6 +157,11 @@ __global__ __launch_bounds__(256) void dice_grad4_kernel(const float* __restrict
             ok[u] = v < total;
             xv[u] = ok[u] ? *reinterpret_cast<const float4*>(x + v * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
             tv[u] = ok[u] ? TV4<TT>::f(*reinterpret_cast<const TQ*>(t + v * 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (MASKED) {
+                const int64_t plane = ok[u] ? v / nv : 0;
+                mv[u] = ok[u] ? *reinterpret_cast<const uchar4*>(valid + (size_t)(plane / k) * hw + (size_t)(v - plane * nv) * 4)
+                              : make_uchar4(0, 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -151,6 +177,7 @@ __global__ __launch_bounds__(256) void dice_grad4_kernel(const float* __restrict
             } else {
                 o.x = g * tv[u].x / eps; o.y = g * tv[u].y / eps; o.z = g * tv[u].z / eps; o.w = g * tv[u].w / eps;
             }
+            if constexpr (MASKED) o = keep4(o, mv[u]);
             *reinterpret_cast<float4*>(dx + v * 4) = o;
         }
     }
@@ -161,16 +188,23 @@ __global__ __launch_bounds__(256) void dice_grad4_kernel(const float* __restrict
 // Per sample: prediction = one-hot of the first arg-max over channels (input > 0.5 for a single channel), per class
 // |P & T| / max(|P | T|, 1e-8) on the byte-converted target, mean over classes, then over samples.  One sweep: integer
 // counts per (sample, class) through wave reductions and integer atomics (exact, order-free), then one tiny finalise.
-template <typename TT>
-__global__ __launch_bounds__(256) void mean_iou_count_kernel(const float* __restrict__ x, const TT* __restrict__ t, int c, int64_t hw,
-                                                           int from_logits, int* __restrict__ counts) {
+// MASKED: pixels with valid == 0 are in neither count; nvalid[b] receives the number of valid pixels of sample b.
+template <typename TT, bool MASKED>
+__global__ __launch_bounds__(256) void mean_iou_count_kernel(const float* __restrict__ x, const TT* __restrict__ t,
+                                                           const uint8_t* __restrict__ valid, int c, int64_t hw, int from_logits,
+                                                           int* __restrict__ counts, int* __restrict__ nvalid) {
     constexpr int kMax = 16;
     const int b = blockIdx.y;
     int inter[kMax], uni[kMax];
 #pragma unroll
     for (int k = 0; k < kMax; ++k) inter[k] = uni[k] = 0;
+    int seen = 0;
     const size_t base = (size_t)b * c * hw;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
+        if constexpr (MASKED) {
+            if (!valid[(size_t)b * hw + i]) continue;
+            ++seen;
+        }
         int arg = 0;
         if (c == 1) {
             arg = x[base + i] > 0.5f ? 0 : -1;
@@ -213,18 +247,31 @@ __global__ __launch_bounds__(256) void mean_iou_count_kernel(const float* __rest
             atomicAdd(counts + ((size_t)b * c + k) * 2 + 1, u);
         }
     }
+    if constexpr (MASKED) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) seen += __shfl_xor(seen, o, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(nvalid + b, seen);
+    }
 }
 
-__global__ void mean_iou_finalize_kernel(const int* __restrict__ counts, int n, int c, float* __restrict__ out) {
+// MASKED: the mean is over the samples that have a valid pixel; NaN when there is none
+template <bool MASKED>
+__global__ void mean_iou_finalize_kernel(const int* __restrict__ counts, const int* __restrict__ nvalid, int n, int c,
+                                         float* __restrict__ out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float total = 0.f;
+    int kept = n;
     for (int b = 0; b < n; ++b) {
+        if constexpr (MASKED) {
+            if (nvalid[b] == 0) { --kept; continue; }
+        }
         float s = 0.f;
         for (int k = 0; k < c; ++k)
             s += (float)counts[((size_t)b * c + k) * 2] / fmaxf((float)counts[((size_t)b * c + k) * 2 + 1], 1e-8f);
         total += s / (float)c;
     }
-    *out = total / (float)n;
+    if constexpr (MASKED) *out = kept ? total / (float)kept : __builtin_nanf("");
+    else *out = total / (float)n;
 }
 
 
@@ -244,77 +291,163 @@ __global__ void onehot_kernel(const uint8_t* __restrict__ lab, int k, int64_t hw
     }
 }
 
+// the same one-hot bytes and, in the same sweep, valid (n, hw) uint8 = labels != ignore.  vec: hw % 4 == 0 and all three
+// pointers 4-byte aligned
+__global__ void onehot_valid_kernel(const uint8_t* __restrict__ lab, int k, int64_t hw, int ignore, bool vec, uint8_t* __restrict__ out,
+                                    uint8_t* __restrict__ valid) {
+    const int b = blockIdx.y;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < hw; i += (int64_t)gridDim.x * blockDim.x * 4) {
+        if (vec) {
+            const uchar4 l = *reinterpret_cast<const uchar4*>(lab + (size_t)b * hw + i);
+            for (int c = 0; c < k; ++c)
+                *reinterpret_cast<uchar4*>(out + ((size_t)b * k + c) * hw + i) =
+                    make_uchar4(l.x == c, l.y == c, l.z == c, l.w == c);
+            *reinterpret_cast<uchar4*>(valid + (size_t)b * hw + i) =
+                make_uchar4(l.x != ignore, l.y != ignore, l.z != ignore, l.w != ignore);
+        } else {
+            for (int64_t j = i; j < min(hw, i + 4); ++j) {
+                const int l = lab[(size_t)b * hw + j];
+                for (int c = 0; c < k; ++c) out[((size_t)b * k + c) * hw + j] = l == c;
+                valid[(size_t)b * hw + j] = l != ignore;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" size_t vs_dice_workspace(int classes) { return ((size_t)kBlocks * classes * 3 + 2 * (size_t)classes) * sizeof(float); }
 
 // loss (1 float, device) and per-class stats are produced by the forward; the backward multiplies by *grad_out (device
 // scalar, may be null = 1).  target_is_f32: targets are fp32 (the reference passes targets.float()) instead of uint8.
-extern "C" int vs_dice_loss_fwd(const float* logits, const void* targets, int target_is_f32, int n, int classes, int64_t hw,
-                                float eps, float* loss, float* workspace, size_t workspace_bytes, void* stream) {
-    VS_REQUIRE(logits && targets && loss && workspace && workspace_bytes >= vs_dice_workspace(classes) && classes >= 1,
-               "dice_loss_fwd: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
+// The launches of the forward and the backward, once for both forms: MASKED = false is what vs_dice_loss_fwd / _bwd run (valid is
+// null and never read), MASKED = true is the same choice of kernels with the mask's alignment added to the 16-byte condition.
+namespace {
+
+template <bool MASKED>
+int dice_fwd_launch(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n, int classes, int64_t hw,
+                    float eps, float* loss, float* workspace, hipStream_t s) {
     float* stats = workspace + (size_t)kBlocks * classes * 3;
-    const bool vec4 = (hw & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)targets & (target_is_f32 ? 15 : 3)) == 0;
+    const bool vec4 = (hw & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)targets & (target_is_f32 ? 15 : 3)) == 0 &&
+                      (!MASKED || ((uintptr_t)valid & 3) == 0);
     if (vec4 && target_is_f32)
-        hipLaunchKernelGGL(dice_partial4_kernel<float>, dim3(kBlocks), dim3(256), 0, s, logits, (const float*)targets, n, classes, hw, workspace);
+        hipLaunchKernelGGL((dice_partial4_kernel<float, MASKED>), dim3(kBlocks), dim3(256), 0, s, logits, (const float*)targets, valid, n, classes, hw, workspace);
     else if (vec4)
-        hipLaunchKernelGGL(dice_partial4_kernel<uint8_t>, dim3(kBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, n, classes, hw, workspace);
+        hipLaunchKernelGGL((dice_partial4_kernel<uint8_t, MASKED>), dim3(kBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, n, classes, hw, workspace);
     else if (target_is_f32)
-        hipLaunchKernelGGL(dice_partial_kernel<float>, dim3(kBlocks), dim3(256), 0, s, logits, (const float*)targets, n, classes, hw, workspace);
+        hipLaunchKernelGGL((dice_partial_kernel<float, MASKED>), dim3(kBlocks), dim3(256), 0, s, logits, (const float*)targets, valid, n, classes, hw, workspace);
     else
-        hipLaunchKernelGGL(dice_partial_kernel<uint8_t>, dim3(kBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, n, classes, hw, workspace);
+        hipLaunchKernelGGL((dice_partial_kernel<uint8_t, MASKED>), dim3(kBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, n, classes, hw, workspace);
     VS_LAUNCH_CHECK();
     hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, kBlocks, classes, eps, stats, loss);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
 
-extern "C" int vs_dice_loss_bwd(const float* logits, const void* targets, int target_is_f32, const float* grad_out, int n,
-                                int classes, int64_t hw, float eps, const float* workspace, float* dlogits, void* stream) {
-    VS_REQUIRE(logits && targets && workspace && dlogits, "dice_loss_bwd: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
+template <bool MASKED>
+int dice_bwd_launch(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, const float* grad_out, int n,
+                    int classes, int64_t hw, float eps, const float* workspace, float* dlogits, hipStream_t s) {
     const float* stats = workspace + (size_t)kBlocks * classes * 3;
     const int64_t total = (int64_t)n * classes * hw;
     const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    const bool vec4 = (hw & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dlogits & 15) == 0 && ((uintptr_t)targets & (target_is_f32 ? 15 : 3)) == 0;
+    const bool vec4 = (hw & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dlogits & 15) == 0 &&
+                      ((uintptr_t)targets & (target_is_f32 ? 15 : 3)) == 0 && (!MASKED || ((uintptr_t)valid & 3) == 0);
     const int grid4 = (int)std::min<int64_t>(4096, (total / 4 + 511) / 512);
     if (vec4 && target_is_f32)
-        hipLaunchKernelGGL(dice_grad4_kernel<float>, dim3(grid4), dim3(256), 0, s, logits, (const float*)targets, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad4_kernel<float, MASKED>), dim3(grid4), dim3(256), 0, s, logits, (const float*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
     else if (vec4)
-        hipLaunchKernelGGL(dice_grad4_kernel<uint8_t>, dim3(grid4), dim3(256), 0, s, logits, (const uint8_t*)targets, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad4_kernel<uint8_t, MASKED>), dim3(grid4), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
     else if (target_is_f32)
-        hipLaunchKernelGGL(dice_grad_kernel<float>, dim3(grid), dim3(256), 0, s, logits, (const float*)targets, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad_kernel<float, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const float*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
     else
-        hipLaunchKernelGGL(dice_grad_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad_kernel<uint8_t, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
 
+template <bool MASKED>
+int mean_iou_launch(const float* input, const void* targets, int target_is_f32, const uint8_t* valid, int from_logits, int n, int classes,
+                    int64_t hw, float* out, void* workspace, size_t zeroed_bytes, hipStream_t s) {
+    VS_CHECK_HIP(hipMemsetAsync(workspace, 0, zeroed_bytes, s));
+    int* counts = (int*)workspace;
+    int* nvalid = counts + (size_t)n * classes * 2;      // MASKED only: the workspace of the unmasked form ends before it
+    const dim3 grid((unsigned)std::min<int64_t>(64, (hw + 255) / 256), (unsigned)n);
+    if (target_is_f32)
+        hipLaunchKernelGGL((mean_iou_count_kernel<float, MASKED>), grid, dim3(256), 0, s, input, (const float*)targets, valid, classes, hw, from_logits, counts, nvalid);
+    else
+        hipLaunchKernelGGL((mean_iou_count_kernel<uint8_t, MASKED>), grid, dim3(256), 0, s, input, (const uint8_t*)targets, valid, classes, hw, from_logits, counts, nvalid);
+    VS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mean_iou_finalize_kernel<MASKED>, dim3(1), dim3(64), 0, s, (const int*)counts, (const int*)nvalid, n, classes, out);
+    VS_LAUNCH_CHECK();
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" int vs_dice_loss_fwd(const float* logits, const void* targets, int target_is_f32, int n, int classes, int64_t hw,
+                                float eps, float* loss, float* workspace, size_t workspace_bytes, void* stream) {
+    VS_REQUIRE(logits && targets && loss && workspace && workspace_bytes >= vs_dice_workspace(classes) && classes >= 1,
+               "dice_loss_fwd: bad arguments");
+    return dice_fwd_launch<false>(logits, targets, target_is_f32, nullptr, n, classes, hw, eps, loss, workspace, (hipStream_t)stream);
+}
+
+extern "C" int vs_dice_loss_bwd(const float* logits, const void* targets, int target_is_f32, const float* grad_out, int n,
+                                int classes, int64_t hw, float eps, const float* workspace, float* dlogits, void* stream) {
+    VS_REQUIRE(logits && targets && workspace && dlogits, "dice_loss_bwd: bad arguments");
+    return dice_bwd_launch<false>(logits, targets, target_is_f32, nullptr, grad_out, n, classes, hw, eps, workspace, dlogits,
+                                  (hipStream_t)stream);
+}
+
+extern "C" int vs_dice_loss_fwd_masked(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n,
+                                       int classes, int64_t hw, float eps, float* loss, float* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    VS_REQUIRE(logits && targets && valid && loss && workspace && workspace_bytes >= vs_dice_workspace(classes) && classes >= 1,
+               "dice_loss_fwd_masked: bad arguments");
+    return dice_fwd_launch<true>(logits, targets, target_is_f32, valid, n, classes, hw, eps, loss, workspace, (hipStream_t)stream);
+}
+
+extern "C" int vs_dice_loss_bwd_masked(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                                       const float* grad_out, int n, int classes, int64_t hw, float eps, const float* workspace,
+                                       float* dlogits, void* stream) {
+    VS_REQUIRE(logits && targets && valid && workspace && dlogits, "dice_loss_bwd_masked: bad arguments");
+    return dice_bwd_launch<true>(logits, targets, target_is_f32, valid, grad_out, n, classes, hw, eps, workspace, dlogits,
+                                 (hipStream_t)stream);
+}
+
 extern "C" size_t vs_mean_iou_workspace(int n, int classes) { return (size_t)n * classes * 2 * sizeof(int); }
+extern "C" size_t vs_mean_iou_masked_workspace(int n, int classes) { return vs_mean_iou_workspace(n, classes) + (size_t)n * sizeof(int); }
 
 extern "C" int vs_mean_iou(const float* input, const void* targets, int target_is_f32, int from_logits, int n, int classes, int64_t hw,
                            float* out, void* workspace, size_t workspace_bytes, void* stream) {
     VS_REQUIRE(input && targets && out && n >= 1 && classes >= 1 && classes <= 16 && hw >= 1, "mean_iou: bad arguments");
     VS_REQUIRE(workspace && workspace_bytes >= vs_mean_iou_workspace(n, classes), "mean_iou: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    VS_CHECK_HIP(hipMemsetAsync(workspace, 0, vs_mean_iou_workspace(n, classes), s));
-    const dim3 grid((unsigned)std::min<int64_t>(64, (hw + 255) / 256), (unsigned)n);
-    if (target_is_f32)
-        hipLaunchKernelGGL(mean_iou_count_kernel<float>, grid, dim3(256), 0, s, input, (const float*)targets, classes, hw, from_logits, (int*)workspace);
-    else
-        hipLaunchKernelGGL(mean_iou_count_kernel<uint8_t>, grid, dim3(256), 0, s, input, (const uint8_t*)targets, classes, hw, from_logits, (int*)workspace);
-    VS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mean_iou_finalize_kernel, dim3(1), dim3(64), 0, s, (const int*)workspace, n, classes, out);
-    VS_LAUNCH_CHECK();
-    return VS_OK;
+    return mean_iou_launch<false>(input, targets, target_is_f32, nullptr, from_logits, n, classes, hw, out, workspace,
+                                  vs_mean_iou_workspace(n, classes), (hipStream_t)stream);
+}
+
+extern "C" int vs_mean_iou_masked(const float* input, const void* targets, int target_is_f32, const uint8_t* valid, int from_logits,
+                                  int n, int classes, int64_t hw, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    VS_REQUIRE(input && targets && valid && out && n >= 1 && classes >= 1 && classes <= 16 && hw >= 1, "mean_iou_masked: bad arguments");
+    VS_REQUIRE(workspace && workspace_bytes >= vs_mean_iou_masked_workspace(n, classes), "mean_iou_masked: workspace too small");
+    return mean_iou_launch<true>(input, targets, target_is_f32, valid, from_logits, n, classes, hw, out, workspace,
+                                 vs_mean_iou_masked_workspace(n, classes), (hipStream_t)stream);
 }
 
 extern "C" int vs_onehot_u8(const uint8_t* labels, int n, int classes, int64_t hw, uint8_t* onehot, void* stream) {
     VS_REQUIRE(labels && onehot && n >= 1 && classes >= 1 && classes <= 255 && hw >= 1, "onehot: bad arguments");
     const dim3 grid((unsigned)std::min<int64_t>(256, (hw / 4 + 255) / 256 + 1), (unsigned)n);
     hipLaunchKernelGGL(onehot_kernel, grid, dim3(256), 0, (hipStream_t)stream, labels, classes, hw, onehot);
+    VS_LAUNCH_CHECK();
+    return VS_OK;
+}
+
+extern "C" int vs_onehot_valid_u8(const uint8_t* labels, int n, int classes, int64_t hw, int ignore, uint8_t* onehot, uint8_t* valid,
+                                  void* stream) {
+    VS_REQUIRE(labels && onehot && valid && n >= 1 && classes >= 1 && classes <= 255 && hw >= 1 && ignore >= 0 && ignore <= 255,
+               "onehot_valid: bad arguments");
+    const bool vec = (hw & 3) == 0 && (((uintptr_t)labels | (uintptr_t)onehot | (uintptr_t)valid) & 3) == 0;
+    const dim3 grid((unsigned)std::min<int64_t>(256, (hw / 4 + 255) / 256 + 1), (unsigned)n);
+    hipLaunchKernelGGL(onehot_valid_kernel, grid, dim3(256), 0, (hipStream_t)stream, labels, classes, hw, ignore, vec, onehot, valid);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
@@ -335,16 +468,24 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
 // BCEWithLogits element: max(x, 0) - x t + log(1 + exp(-|x|))   (torch's stable form)
 __device__ __forceinline__ float bce_elem(float x, float t) { return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x))); }
 
-template <typename TT>
-__global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restrict__ x, const TT* __restrict__ t, int kind, int n, int k,
-                                                        int64_t hw, float* __restrict__ partial) {
+// MASKED: block_valid[block] receives the number of valid pixels the block saw (counted in class 0's pass, in integers): their sum
+// is M, which the finalise uses where the unmasked form is handed n hw and n k hw by the host.
+template <typename TT, bool MASKED>
+__global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restrict__ x, const TT* __restrict__ t,
+                                                        const uint8_t* __restrict__ valid, int kind, int n, int k, int64_t hw,
+                                                        float* __restrict__ partial, int* __restrict__ block_valid) {
     __shared__ float red[kSegSums][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int seen = 0;
     for (int c = 0; c < k; ++c) {
         float s[kSegSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (int b = 0; b < n; ++b) {
             const size_t base = ((size_t)b * k + c) * hw;
             for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (int64_t)gridDim.x * 256) {
+                if constexpr (MASKED) {
+                    if (!valid[(size_t)b * hw + i]) continue;
+                    if (c == 0) ++seen;
+                }
                 const float xv = x[base + i], tv = tval(t, base + i);
                 if (kind == 3) {
                     if (c == 0) {   // cross entropy is per pixel across the classes: class 0's pass carries it
@@ -379,14 +520,34 @@ __global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restric
                 (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
         __syncthreads();
     }
+    if constexpr (MASKED) {
+        __shared__ int seen_red[4];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) seen += __shfl_xor(seen, o, 64);
+        if (lane == 0) seen_red[wave] = seen;
+        __syncthreads();
+        if (threadIdx.x == 0) block_valid[blockIdx.x] = (seen_red[0] + seen_red[1]) + (seen_red[2] + seen_red[3]);
+    }
 }
 
 // one wave: per-class sums in fp64 (fixed order), the loss, and coef[c] = {a_c, b_c, g_c} + scal = {s}
-__global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restrict__ partial, int nblocks, int kind, int k, double m_elems,
-                                                        double n_pix, float alpha, float beta, float eps, float* __restrict__ coef,
-                                                        float* __restrict__ loss) {
+// MASKED: n_pix = M = the sum of block_valid and m_elems = M k replace the two arguments; with M = 0 the BCE and cross-entropy
+// terms and their gradient scale are 0 (not 0 / 0), the Dice terms follow their formulas (every D <= eps: loss 1).
+template <bool MASKED>
+__global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restrict__ partial, const int* __restrict__ block_valid,
+                                                        int nblocks, int kind, int k, double m_elems, double n_pix, float alpha,
+                                                        float beta, float eps, float* __restrict__ coef, float* __restrict__ loss) {
     const int lane = threadIdx.x;
     __shared__ double S[16][kSegSums];
+    [[maybe_unused]] const double all_pix = n_pix;
+    if constexpr (MASKED) {
+        long long m = 0;
+        for (int b = lane; b < nblocks; b += 64) m += block_valid[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m += __shfl_xor(m, o, 64);
+        n_pix = (double)m;
+        m_elems = (double)m * k;
+    }
     for (int c = 0; c < k; ++c) {
         double s[kSegSums] = {0, 0, 0, 0, 0, 0};
         for (int b = lane; b < nblocks; b += 64) {
@@ -405,13 +566,15 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
     if (lane != 0) return;
     double total = 0.0, bce = 0.0;
     for (int c = 0; c < k; ++c) bce += S[c][5];
+    const bool none = MASKED && n_pix == 0.0;
     float* scal = coef + 16 * 4;
     scal[0] = 0.f;
+    if constexpr (MASKED) scal[1] = 0.f;
     for (int c = 0; c < 16; ++c) coef[c * 4 + 0] = coef[c * 4 + 1] = coef[c * 4 + 2] = coef[c * 4 + 3] = 0.f;
     if (kind == 1 || kind == 2) {
         const double wb = kind == 1 ? (double)alpha : 1.0;
-        total += wb * bce / m_elems;
-        scal[0] = (float)(wb / m_elems);                         // d/dx of the mean BCE: (p - t) / M
+        total += none ? 0.0 : wb * bce / m_elems;
+        scal[0] = none ? 0.f : (float)(wb / m_elems);            // d/dx of the mean BCE: (p - t) / M
         if (kind == 1) {
             double acc = 0.0;
             for (int c = 0; c < k; ++c) {
@@ -426,8 +589,8 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
             total += beta * (1.0 - acc / k);
         }
     } else if (kind == 3) {
-        total = bce / n_pix;
-        scal[0] = (float)(1.0 / n_pix);
+        total = none ? 0.0 : bce / n_pix;
+        scal[0] = none ? 0.f : (float)(1.0 / n_pix);
     } else {   // generalised Dice
         const int kk = k == 1 ? 2 : k;
         double Spt[16], Sp[16], St[16];
@@ -449,6 +612,15 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
         for (int c = 0; c < kk; ++c) { a[c] = -2.0 * w[c] / denom; gg[c] = live[c] ? 2.0 * inter * w[c] / (denom * denom) : 0.0; }
         if (k == 1) {   // p' = 1 - p, t' = 1 - t:  dL/dp = (a0 t + g0) - (a1 (1 - t) + g1) = (a0 + a1) t + (g0 - a1 - g1)
             coef[0] = (float)(a[0] + a[1]); coef[2] = (float)(gg[0] - a[1] - gg[1]);
+            // coef[0] + coef[2] is dL/dp of a foreground pixel, and a1 cancels in it: where every valid pixel is foreground
+            // (w1 = 1 / eps - strokes painted on the object alone) |a1| is a million times the sum, and fp32 coefficients leave
+            // it two or three digits.  As soon as a pixel is ignored the gradient sweep therefore takes the foreground value from
+            // coef[3], formed here in fp64 without a1 (scal[1] says so).  With nothing ignored the masked call is the unmasked
+            // computation, bit for bit.
+            if constexpr (MASKED) {
+                coef[3] = (float)(a[0] + gg[0] - gg[1]);
+                scal[1] = n_pix < all_pix ? 1.f : 0.f;
+            }
         } else {
             for (int c = 0; c < k; ++c) { coef[c * 4 + 0] = (float)a[c]; coef[c * 4 + 2] = (float)gg[c]; }
         }
@@ -456,8 +628,9 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
     *loss = (float)total;
 }
 
-template <typename TT>
-__global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__ x, const TT* __restrict__ t, const float* __restrict__ coef,
+template <typename TT, bool MASKED>
+__global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__ x, const TT* __restrict__ t,
+                                                     const uint8_t* __restrict__ valid, const float* __restrict__ coef,
                                                      const float* __restrict__ gout, int kind, int n, int k, int64_t hw,
                                                      float* __restrict__ dx) {
     const float g = gout ? *gout : 1.f;
@@ -467,6 +640,12 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__
         for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < total; j += (int64_t)gridDim.x * 256) {
             const int64_t b = j / hw, i = j - b * hw;
             const size_t p0 = (size_t)b * k * hw + i;
+            if constexpr (MASKED) {
+                if (!valid[j]) {
+                    for (int q = 0; q < k; ++q) dx[p0 + (size_t)q * hw] = 0.f;
+                    continue;
+                }
+            }
             float m = x[p0];
             for (int q = 1; q < k; ++q) m = fmaxf(m, x[p0 + (size_t)q * hw]);
             float se = 0.f;
@@ -482,48 +661,98 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__
         return;
     }
     const int64_t total = (int64_t)n * k * hw;
+    if constexpr (MASKED) {
+        if (coef[16 * 4 + 1] != 0.f) {
+            // one-class generalised Dice with ignored pixels (seg_finalize_kernel): dL/dp is coef[3] on the foreground and coef[2]
+            // on the background, not their fp32 sum.  A loop of its own, so the one below stays the unmasked loop plus a select.
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+                const float tv = tval(t, i), p = sigmoidf_(x[i]);
+                dx[i] = valid[i] ? g * ((tv != 0.f ? coef[3] : coef[2]) * p * (1.f - p)) : 0.f;      // (k = 1: the pixel index is i)
+            }
+            return;
+        }
+    }
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)((i / hw) % k);
+        const int64_t plane = i / hw;
+        const int c = (int)(plane % k);
         const float xv = x[i], tv = tval(t, i);
         const float p = sigmoidf_(xv);
         const float dldp = coef[c * 4 + 0] * tv + coef[c * 4 + 1] * p + coef[c * 4 + 2];
-        dx[i] = g * (dldp * p * (1.f - p) + sc * (p - tv));
+        const float d = g * (dldp * p * (1.f - p) + sc * (p - tv));
+        // the value is formed for every element and selected at the end: a loop body of the unmasked shape, which the compiler
+        // unrolls and contracts as it does the unmasked one (an early `continue` here gave other roundings in the unrolled trips)
+        if constexpr (MASKED) dx[i] = valid[(size_t)(plane / k) * hw + (i - plane * hw)] ? d : 0.f;
+        else dx[i] = d;
     }
+}
+
+// workspace: partial sums, coef[16 * 4], scal[4] and - the masked form only - one int per block of the reduction
+template <bool MASKED>
+int seg_fwd_launch(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n, int classes,
+                   int64_t hw, float alpha, float beta, float eps, float* loss, float* workspace, hipStream_t s) {
+    float* coef = workspace + (size_t)kSegBlocks * classes * kSegSums;
+    int* block_valid = (int*)(coef + 16 * 4 + 4);
+    if (target_is_f32)
+        hipLaunchKernelGGL((seg_partial_kernel<float, MASKED>), dim3(kSegBlocks), dim3(256), 0, s, logits, (const float*)targets, valid, kind, n, classes, hw, workspace, block_valid);
+    else
+        hipLaunchKernelGGL((seg_partial_kernel<uint8_t, MASKED>), dim3(kSegBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, kind, n, classes, hw, workspace, block_valid);
+    VS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(seg_finalize_kernel<MASKED>, dim3(1), dim3(64), 0, s, workspace, (const int*)block_valid, kSegBlocks, kind, classes,
+                       (double)n * classes * (double)hw, (double)n * (double)hw, alpha, beta, eps, coef, loss);
+    VS_LAUNCH_CHECK();
+    return VS_OK;
+}
+
+template <bool MASKED>
+int seg_bwd_launch(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, const float* grad_out,
+                   int n, int classes, int64_t hw, const float* workspace, float* dlogits, hipStream_t s) {
+    const float* coef = workspace + (size_t)kSegBlocks * classes * kSegSums;
+    const int64_t total = kind == 3 ? (int64_t)n * hw : (int64_t)n * classes * hw;
+    const int grid = (int)std::min<int64_t>(8192, (total + 255) / 256);
+    if (target_is_f32)
+        hipLaunchKernelGGL((seg_grad_kernel<float, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const float*)targets, valid, coef, grad_out, kind, n, classes, hw, dlogits);
+    else
+        hipLaunchKernelGGL((seg_grad_kernel<uint8_t, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, coef, grad_out, kind, n, classes, hw, dlogits);
+    VS_LAUNCH_CHECK();
+    return VS_OK;
 }
 
 }  // namespace
 
 extern "C" size_t vs_seg_loss_workspace(int classes) { return ((size_t)kSegBlocks * classes * kSegSums + 16 * 4 + 4) * sizeof(float); }
+extern "C" size_t vs_seg_loss_masked_workspace(int classes) { return vs_seg_loss_workspace(classes) + kSegBlocks * sizeof(int); }
 
 extern "C" int vs_seg_loss_fwd(int kind, const float* logits, const void* targets, int target_is_f32, int n, int classes, int64_t hw,
                                float alpha, float beta, float eps, float* loss, float* workspace, size_t workspace_bytes, void* stream) {
     VS_REQUIRE(kind >= 1 && kind <= 4, "seg_loss: kind must be 1 (BCE-Dice), 2 (BCE), 3 (cross entropy) or 4 (generalised Dice)");
     VS_REQUIRE(logits && targets && loss && workspace && workspace_bytes >= vs_seg_loss_workspace(classes) && classes >= 1 && classes <= 16,
                "seg_loss_fwd: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    float* coef = workspace + (size_t)kSegBlocks * classes * kSegSums;
-    if (target_is_f32)
-        hipLaunchKernelGGL(seg_partial_kernel<float>, dim3(kSegBlocks), dim3(256), 0, s, logits, (const float*)targets, kind, n, classes, hw, workspace);
-    else
-        hipLaunchKernelGGL(seg_partial_kernel<uint8_t>, dim3(kSegBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, kind, n, classes, hw, workspace);
-    VS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(seg_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, kSegBlocks, kind, classes, (double)n * classes * (double)hw,
-                       (double)n * (double)hw, alpha, beta, eps, coef, loss);
-    VS_LAUNCH_CHECK();
-    return VS_OK;
+    return seg_fwd_launch<false>(kind, logits, targets, target_is_f32, nullptr, n, classes, hw, alpha, beta, eps, loss, workspace,
+                                 (hipStream_t)stream);
 }
 
 extern "C" int vs_seg_loss_bwd(int kind, const float* logits, const void* targets, int target_is_f32, const float* grad_out, int n,
                                int classes, int64_t hw, const float* workspace, float* dlogits, void* stream) {
     VS_REQUIRE(kind >= 1 && kind <= 4 && logits && targets && workspace && dlogits, "seg_loss_bwd: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    const float* coef = workspace + (size_t)kSegBlocks * classes * kSegSums;
-    const int64_t total = kind == 3 ? (int64_t)n * hw : (int64_t)n * classes * hw;
-    const int grid = (int)std::min<int64_t>(8192, (total + 255) / 256);
-    if (target_is_f32)
-        hipLaunchKernelGGL(seg_grad_kernel<float>, dim3(grid), dim3(256), 0, s, logits, (const float*)targets, coef, grad_out, kind, n, classes, hw, dlogits);
-    else
-        hipLaunchKernelGGL(seg_grad_kernel<uint8_t>, dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, coef, grad_out, kind, n, classes, hw, dlogits);
-    VS_LAUNCH_CHECK();
-    return VS_OK;
+    return seg_bwd_launch<false>(kind, logits, targets, target_is_f32, nullptr, grad_out, n, classes, hw, workspace, dlogits,
+                                 (hipStream_t)stream);
+}
+
+extern "C" int vs_seg_loss_fwd_masked(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n,
+                                      int classes, int64_t hw, float alpha, float beta, float eps, float* loss, float* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    VS_REQUIRE(kind >= 1 && kind <= 4, "seg_loss: kind must be 1 (BCE-Dice), 2 (BCE), 3 (cross entropy) or 4 (generalised Dice)");
+    VS_REQUIRE(logits && targets && valid && loss && workspace && classes >= 1 && classes <= 16 &&
+                   workspace_bytes >= vs_seg_loss_masked_workspace(classes),
+               "seg_loss_fwd_masked: bad arguments");
+    return seg_fwd_launch<true>(kind, logits, targets, target_is_f32, valid, n, classes, hw, alpha, beta, eps, loss, workspace,
+                                (hipStream_t)stream);
+}
+
+extern "C" int vs_seg_loss_bwd_masked(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                                      const float* grad_out, int n, int classes, int64_t hw, const float* workspace, float* dlogits,
+                                      void* stream) {
+    VS_REQUIRE(kind >= 1 && kind <= 4 && logits && targets && valid && workspace && dlogits, "seg_loss_bwd_masked: bad arguments");
+    return seg_bwd_launch<true>(kind, logits, targets, target_is_f32, valid, grad_out, n, classes, hw, workspace, dlogits,
+                                (hipStream_t)stream);
 }

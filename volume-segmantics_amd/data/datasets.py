@@ -164,7 +164,8 @@ class ResidentSliceLoader:
     batches (`batch_sampler`, `set_epoch`), it yields (images (b, 1, s, s) uint8, masks (b, s, s) uint8) on the device - what
     `prepare_training_batch` takes for device-side augmentation / normalisation - or None for an empty validation share."""
 
-    def __init__(self, dataset, batch_sampler, device, decode_threads: int = 8):
+    def __init__(self, dataset, batch_sampler, device, decode_threads: int = 8, ignore_label=None):
+        """``ignore_label`` (255 with sparse labels): left out of the label-range check."""
         from concurrent.futures import ThreadPoolExecutor
         self.batch_sampler, self.device = batch_sampler, torch.device(device)
         self.num_labels = None      # set by the trainer: the label-range check of the reference's F.one_hot (see __iter__)
@@ -189,7 +190,8 @@ class ResidentSliceLoader:
         with ThreadPoolExecutor(max_workers=max(1, decode_threads)) as pool:      # PIL releases the GIL while it decodes
             list(pool.map(decode, range(n)))
         self.images, self.masks = images.to(self.device), masks.to(self.device)
-        self.max_label = int(self.masks.max())      # one device reduction per loader, nothing per step
+        # one device reduction per loader, nothing per step
+        self.max_label = int(self.masks.max()) if ignore_label is None else utils.max_real_label(self.masks, ignore_label)
 
     @staticmethod
     def bytes_needed(n: int, image_size: int) -> int:
@@ -255,6 +257,8 @@ def get_2d_training_dataloaders(image_dir: Path, label_dir: Path, settings, rank
         valid_raw = VolSeg2dDataset(image_dir, label_dir, settings.image_size, augment="device")      # raw pairs: normalised on the device
         ts = ShardedBatchSampler(cut, batch_size, rank, world, shuffle=True, drop_last=True, seed=seed + 1)
         vs = ShardedBatchSampler(n - cut, batch_size, rank, world, shuffle=False, drop_last=False)
-        return (ResidentSliceLoader(Subset(train_full, indices[:cut]), ts, dev), ResidentSliceLoader(Subset(valid_raw, indices[cut:]), vs, dev))
+        ignore = utils.IGNORE_INDEX if getattr(settings, "ignore_label", None) is not None else None
+        return (ResidentSliceLoader(Subset(train_full, indices[:cut]), ts, dev, ignore_label=ignore),
+                ResidentSliceLoader(Subset(valid_raw, indices[cut:]), vs, dev, ignore_label=ignore))
     return make_training_loaders(Subset(train_full, indices[:cut]), Subset(valid_full, indices[cut:]), batch_size, rank, world,
                                  seed=seed + 1, num_workers=workers, pin_memory=cfg.PIN_CUDA_MEMORY and torch.cuda.is_available())

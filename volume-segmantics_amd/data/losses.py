@@ -12,10 +12,44 @@ def _per_channel(t: torch.Tensor) -> torch.Tensor:
     return t.transpose(0, 1).reshape(t.size(1), -1)
 
 
-def compute_per_channel_dice(input, target, epsilon=1e-6, weight=None):
+# ---- sparse labels ---------------------------------------------------------------------------------------------------------------
+# ``valid`` (N, H, W) or (N, H*W), uint8 or bool: 1 where the pixel carries a label (the settings key ``ignore_label``).  Every
+# criterion is a function of sums over pixels; with a mask m each sum runs over the valid pixels only, M = sum m replaces the pixel
+# count, and an ignored pixel has a gradient of exactly 0.  No pixel valid (M = 0): the BCE and cross-entropy terms are 0, the Dice
+# terms follow their formulas (every denominator is clamped: loss 1) - on purpose not torch's NaN, which would stay in AdamW's
+# moments for good.  Values are selected (torch.where), not multiplied, and the logits of ignored pixels are replaced by 0 before
+# any function of them is formed, so a non-finite logit under an ignored pixel stays out of the sums and of the gradients.
+def _mask_like(valid, ref):
+    """valid as a bool tensor that broadcasts against ref (N, C, ...)"""
+    return (valid.reshape(valid.shape[0], 1, -1) != 0).reshape((ref.shape[0], 1) + tuple(ref.shape[2:]))
+
+
+def _keep(t, mask):
+    return torch.where(mask, t, torch.zeros((), dtype=t.dtype, device=t.device))
+
+
+def masked_bce_with_logits(input, target, valid):
+    """BCEWithLogitsLoss over the valid pixels: sum / (M K); 0 when M = 0."""
+    mask = _mask_like(valid, input)
+    elem = nn.functional.binary_cross_entropy_with_logits(_keep(input, mask), target.to(input.dtype), reduction="none")
+    return _keep(elem, mask).sum() / (mask.sum() * input.size(1)).clamp(min=1)
+
+
+def masked_cross_entropy(input, target, valid):
+    """CrossEntropyLoss over the valid pixels, the class index the arg-max of the one-hot target: sum / M - what
+    nn.CrossEntropyLoss(ignore_index=...) computes - and 0 when M = 0."""
+    mask = _mask_like(valid, input)
+    elem = nn.functional.cross_entropy(_keep(input, mask), torch.argmax(target, dim=1), reduction="none").unsqueeze(1)
+    return _keep(elem, mask).sum() / mask.sum().clamp(min=1)
+
+
+def compute_per_channel_dice(input, target, epsilon=1e-6, weight=None, valid=None):
     """2 * sum(x t) / clamp(sum(x^2) + sum(t^2)) per channel (V-Net form, pytorch3dunet_losses.py:15-41)."""
     if input.size() != target.size():
         raise ValueError("'input' and 'target' must have the same shape")
+    if valid is not None:
+        mask = _mask_like(valid, input)
+        input, target = _keep(input, mask), _keep(target.float(), mask)
     x, t = _per_channel(input), _per_channel(target).float()
     inter = (x * t).sum(-1)
     if weight is not None:
@@ -35,15 +69,28 @@ class DiceLoss(nn.Module):
         self.register_buffer("weight", weight)
         self.normalization = {"sigmoid": torch.sigmoid, "softmax": lambda x: torch.softmax(x, 1), "none": lambda x: x}[normalization]
 
-    def forward(self, input, target):
-        return 1.0 - torch.mean(compute_per_channel_dice(self.normalization(input), target, weight=self.weight))
+    def forward(self, input, target, valid=None):
+        if valid is not None:
+            input = _keep(input, _mask_like(valid, input))
+        return 1.0 - torch.mean(compute_per_channel_dice(self.normalization(input), target, weight=self.weight, valid=valid))
+
+
+def _valid_u8(valid, n, hw):
+    """the mask as the kernels read it: contiguous uint8, n * hw elements"""
+    if valid.dtype != torch.uint8:
+        valid = (valid != 0).to(torch.uint8)
+    valid = valid.contiguous()
+    if valid.numel() != n * hw:
+        raise ValueError(f"valid has {valid.numel()} elements for {n} samples of {hw} pixels")
+    return valid
 
 
 class _FusedDiceFn(torch.autograd.Function):
-    """DiceLoss(normalization="none") forward + gradient as two HIP sweeps (vs_dice_loss_fwd / _bwd)."""
+    """DiceLoss(normalization="none") forward + gradient as two HIP sweeps (vs_dice_loss_fwd / _bwd; with ``valid`` their _masked
+    forms, which leave the same per-class sums in the workspace)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, eps, group=None):
+    def forward(ctx, logits, targets, eps, group=None, valid=None):
         from .. import _lib
         n, k = logits.shape[:2]
         hw = logits[0, 0].numel()
@@ -54,8 +101,13 @@ class _FusedDiceFn(torch.autograd.Function):
             targets, is_f32 = targets.float(), True
         ws = torch.empty(_lib.lib.vs_dice_workspace(k) // 4, dtype=torch.float32, device=logits.device)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        _lib.check(_lib.lib.vs_dice_loss_fwd(_lib.ptr(logits), _lib.ptr(targets), int(is_f32), n, k, hw, eps, _lib.ptr(loss),
-                                            _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()))
+        if valid is None:
+            _lib.check(_lib.lib.vs_dice_loss_fwd(_lib.ptr(logits), _lib.ptr(targets), int(is_f32), n, k, hw, eps, _lib.ptr(loss),
+                                                _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()))
+        else:
+            valid = _valid_u8(valid, n, hw)
+            _lib.check(_lib.lib.vs_dice_loss_fwd_masked(_lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(valid), n, k, hw, eps,
+                                                       _lib.ptr(loss), _lib.ptr(ws), ws.numel() * 4, _lib.stream_ptr()))
         world = 1
         if group is not None:
             import torch.distributed as dist
@@ -67,22 +119,26 @@ class _FusedDiceFn(torch.autograd.Function):
             dist.all_reduce(stats, group=group)
             inter, denom = stats.view(k, 2)[:, 0].double(), stats.view(k, 2)[:, 1].double()
             loss = (1.0 - (2.0 * inter / denom.clamp(min=eps)).mean()).float()
-        ctx.save_for_backward(logits, targets, ws)
+        ctx.save_for_backward(logits, targets, ws, *(() if valid is None else (valid,)))
         ctx.meta = (n, k, hw, eps, is_f32, world)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         from .. import _lib
-        logits, targets, ws = ctx.saved_tensors
+        logits, targets, ws, *valid = ctx.saved_tensors
         n, k, hw, eps, is_f32, world = ctx.meta
         dx = torch.empty_like(logits)
         # (global Dice: every rank holds d loss / d its own logits; the gradient all-reduce AVERAGES the ranks' parameter gradients,
         # the global loss wants their SUM)
         g = (grad_out if world == 1 else grad_out * float(world)).contiguous().float()    # (one rank: no multiply launch)
-        _lib.check(_lib.lib.vs_dice_loss_bwd(_lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(g), n, k, hw, eps,
-                                            _lib.ptr(ws), _lib.ptr(dx), _lib.stream_ptr()))
-        return dx, None, None, None
+        if not valid:
+            _lib.check(_lib.lib.vs_dice_loss_bwd(_lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(g), n, k, hw, eps,
+                                                _lib.ptr(ws), _lib.ptr(dx), _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib.vs_dice_loss_bwd_masked(_lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(valid[0]), _lib.ptr(g),
+                                                       n, k, hw, eps, _lib.ptr(ws), _lib.ptr(dx), _lib.stream_ptr()))
+        return dx, None, None, None, None
 
 
 class HipDiceLoss(nn.Module):
@@ -97,14 +153,16 @@ class HipDiceLoss(nn.Module):
         self.global_group = global_group
         self._torch = DiceLoss(normalization="none")
 
-    def forward(self, input, target):
+    def forward(self, input, target, valid=None):
         if input.is_cuda and input.dtype == torch.float32 and input.dim() >= 3 and input.shape == target.shape:
             # the cross-rank Dice is a TRAINING construct (it pairs with SyncBatchNorm's global batch): under torch.no_grad() - the
             # validation loop - every rank evaluates its own batches, whose count can differ between ranks when the last global
             # batch is partial (a rank with an empty share skips it), so a collective there would be mismatched across ranks
             group = self.global_group if (torch.is_grad_enabled() and input.requires_grad) else None
-            return _FusedDiceFn.apply(input, target, self.epsilon, group)
-        return self._torch(input, target)
+            if valid is None:
+                return _FusedDiceFn.apply(input, target, self.epsilon, group)
+            return _FusedDiceFn.apply(input, target, self.epsilon, group, valid)
+        return self._torch(input, target, valid)
 
 
 class GeneralizedDiceLoss(nn.Module):
@@ -115,10 +173,15 @@ class GeneralizedDiceLoss(nn.Module):
         self.epsilon = epsilon
         self.normalization = {"sigmoid": torch.sigmoid, "softmax": lambda x: torch.softmax(x, 1), "none": lambda x: x}[normalization]
 
-    def forward(self, input, target):
+    def forward(self, input, target, valid=None):
+        if valid is not None:
+            input = _keep(input, _mask_like(valid, input))
         x, t = _per_channel(self.normalization(input)), _per_channel(target).float()
         if x.size(0) == 1:  # put foreground and background in separate channels
             x, t = torch.cat((x, 1 - x), 0), torch.cat((t, 1 - t), 0)
+        if valid is not None:      # after the complement, so that 1 - p and 1 - t of an ignored pixel are left out too
+            mask = (valid.reshape(1, -1) != 0)
+            x, t = _keep(x, mask), _keep(t, mask)
         w = t.sum(-1)
         w = (1 / (w * w).clamp(min=self.epsilon)).detach()
         inter = ((x * t).sum(-1) * w).sum()
@@ -132,7 +195,9 @@ class BCEDiceLoss(nn.Module):
         self.alpha, self.beta = alpha, beta
         self.bce, self.dice = nn.BCEWithLogitsLoss(), DiceLoss()
 
-    def forward(self, input, target):
+    def forward(self, input, target, valid=None):
+        if valid is not None:
+            return self.alpha * masked_bce_with_logits(input, target, valid) + self.beta * self.dice(input, target, valid)
         return self.alpha * self.bce(input, target) + self.beta * self.dice(input, target)
 
 
@@ -140,7 +205,7 @@ class _FusedSegLossFn(torch.autograd.Function):
     """BCE-Dice / BCE / cross entropy / generalised Dice as one HIP reduction sweep + one gradient sweep (vs_seg_loss_fwd / _bwd)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, kind, alpha, beta, eps):
+    def forward(ctx, logits, targets, kind, alpha, beta, eps, valid=None):
         from .. import _lib
         n, k = logits.shape[:2]
         hw = logits[0, 0].numel()
@@ -149,25 +214,35 @@ class _FusedSegLossFn(torch.autograd.Function):
         is_f32 = targets.dtype == torch.float32
         if not is_f32 and targets.dtype != torch.uint8:
             targets, is_f32 = targets.float(), True
-        nbytes = _lib.lib.vs_seg_loss_workspace(k)
+        nbytes = _lib.lib.vs_seg_loss_workspace(k) if valid is None else _lib.lib.vs_seg_loss_masked_workspace(k)
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=logits.device)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        _lib.check(_lib.lib.vs_seg_loss_fwd(kind, _lib.ptr(logits), _lib.ptr(targets), int(is_f32), n, k, hw, float(alpha), float(beta),
-                                           float(eps), _lib.ptr(loss), _lib.ptr(ws), nbytes, _lib.stream_ptr()))
-        ctx.save_for_backward(logits, targets, ws)
+        if valid is None:
+            _lib.check(_lib.lib.vs_seg_loss_fwd(kind, _lib.ptr(logits), _lib.ptr(targets), int(is_f32), n, k, hw, float(alpha), float(beta),
+                                               float(eps), _lib.ptr(loss), _lib.ptr(ws), nbytes, _lib.stream_ptr()))
+        else:
+            valid = _valid_u8(valid, n, hw)
+            _lib.check(_lib.lib.vs_seg_loss_fwd_masked(kind, _lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(valid), n, k, hw,
+                                                      float(alpha), float(beta), float(eps), _lib.ptr(loss), _lib.ptr(ws), nbytes,
+                                                      _lib.stream_ptr()))
+        ctx.save_for_backward(logits, targets, ws, *(() if valid is None else (valid,)))
         ctx.meta = (kind, n, k, hw, is_f32)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         from .. import _lib
-        logits, targets, ws = ctx.saved_tensors
+        logits, targets, ws, *valid = ctx.saved_tensors
         kind, n, k, hw, is_f32 = ctx.meta
         dx = torch.empty_like(logits)
         g = grad_out.contiguous().float()
-        _lib.check(_lib.lib.vs_seg_loss_bwd(kind, _lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(g), n, k, hw, _lib.ptr(ws),
-                                           _lib.ptr(dx), _lib.stream_ptr()))
-        return dx, None, None, None, None, None
+        if not valid:
+            _lib.check(_lib.lib.vs_seg_loss_bwd(kind, _lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(g), n, k, hw, _lib.ptr(ws),
+                                               _lib.ptr(dx), _lib.stream_ptr()))
+        else:
+            _lib.check(_lib.lib.vs_seg_loss_bwd_masked(kind, _lib.ptr(logits), _lib.ptr(targets), int(is_f32), _lib.ptr(valid[0]), _lib.ptr(g),
+                                                      n, k, hw, _lib.ptr(ws), _lib.ptr(dx), _lib.stream_ptr()))
+        return dx, None, None, None, None, None, None
 
 
 class HipSegLoss(nn.Module):
@@ -184,21 +259,35 @@ class HipSegLoss(nn.Module):
         self.fallback = {"BCEDiceLoss": lambda: BCEDiceLoss(alpha, beta), "BCELoss": nn.BCEWithLogitsLoss,
                          "CrossEntropyLoss": nn.CrossEntropyLoss, "GeneralizedDiceLoss": lambda: GeneralizedDiceLoss(epsilon=epsilon)}[kind]()
 
-    def forward(self, input, target):
+    def forward(self, input, target, valid=None):
         if (input.is_cuda and input.dtype == torch.float32 and input.dim() >= 3 and input.shape == target.shape
                 and input.size(1) <= 16):
-            return _FusedSegLossFn.apply(input, target, self.KINDS[self.kind], self.alpha, self.beta, self.epsilon)
+            if valid is None:
+                return _FusedSegLossFn.apply(input, target, self.KINDS[self.kind], self.alpha, self.beta, self.epsilon)
+            return _FusedSegLossFn.apply(input, target, self.KINDS[self.kind], self.alpha, self.beta, self.epsilon, valid)
+        if valid is not None:
+            return masked_criterion(self.fallback, input, target, valid)
         if self.kind == "CrossEntropyLoss":
             return self.fallback(input, torch.argmax(target, dim=1))
         return self.fallback(input, target.float())
+
+
+def masked_criterion(criterion, input, target, valid):
+    """One of the trainer's torch criteria on one-hot targets with a validity mask: the restatements of this module take the mask
+    themselves, torch's own BCE-with-logits and cross entropy are replaced by their masked forms."""
+    if isinstance(criterion, nn.BCEWithLogitsLoss):
+        return masked_bce_with_logits(input, target, valid)
+    if isinstance(criterion, nn.CrossEntropyLoss):
+        return masked_cross_entropy(input, target, valid)
+    return criterion(input, target.float(), valid)
 
 
 class DiceCoefficient:
     def __init__(self, epsilon=1e-6, **kwargs):
         self.epsilon = epsilon
 
-    def __call__(self, input, target):
-        return torch.mean(compute_per_channel_dice(input.flatten(2), target.flatten(2), epsilon=self.epsilon))
+    def __call__(self, input, target, valid=None):
+        return torch.mean(compute_per_channel_dice(input.flatten(2), target.flatten(2), epsilon=self.epsilon, valid=valid))
 
 
 class MeanIoU:
@@ -206,20 +295,27 @@ class MeanIoU:
     Accepts the (N, C, 1, H, W) tensors the reference's trainer builds or plain (N, C, H, W).  GPU tensors go through
     one HIP sweep (vs_mean_iou); the torch ops below serve CPU tensors and the skip_channels / ignore_index options."""
 
-    def from_logits(self, logits, target):
+    def from_logits(self, logits, target, valid=None):
         """metric(softmax(logits, dim=1), target) - the trainer's validation call - without materialising the softmax."""
         if (logits.is_cuda and logits.dtype == torch.float32 and logits.shape == target.shape and 1 < logits.size(1) <= 16
                 and not self.skip_channels and self.ignore_index is None and target.dtype in (torch.uint8, torch.float32)):
-            return self._hip(logits, target, from_logits=1)
-        return self(torch.softmax(logits, dim=1), target)
+            return self._hip(logits, target, from_logits=1, valid=valid)
+        return self(torch.softmax(logits, dim=1), target, valid)
 
     @staticmethod
-    def _hip(input, target, from_logits=0):
+    def _hip(input, target, from_logits=0, valid=None):
         from .._lib import check, lib, ptr, stream_ptr
         n, c = input.size(0), input.size(1)
         x, t = input.contiguous(), target.contiguous()
         hw = x.numel() // (n * c)
         out = torch.empty((), dtype=torch.float32, device=x.device)
+        if valid is not None:
+            valid = _valid_u8(valid, n, hw)
+            nbytes = lib.vs_mean_iou_masked_workspace(n, c)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+            check(lib.vs_mean_iou_masked(ptr(x), ptr(t), 1 if t.dtype == torch.float32 else 0, ptr(valid), from_logits, n, c, hw, ptr(out),
+                                         ptr(ws), nbytes, stream_ptr()))
+            return out
         nbytes = lib.vs_mean_iou_workspace(n, c)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         check(lib.vs_mean_iou(ptr(x), ptr(t), 1 if t.dtype == torch.float32 else 0, from_logits, n, c, hw, ptr(out), ptr(ws),
@@ -229,22 +325,31 @@ class MeanIoU:
     def __init__(self, skip_channels=(), ignore_index=None, **kwargs):
         self.skip_channels, self.ignore_index = skip_channels, ignore_index
 
-    def __call__(self, input, target):
+    def __call__(self, input, target, valid=None):
+        """``valid``: intersection and union are counted over the valid pixels of each sample; a sample without one is left out of
+        the mean over samples, and the result is NaN when no sample is left."""
         if (input.is_cuda and input.dtype == torch.float32 and input.shape == target.shape and input.size(1) <= 16
                 and not self.skip_channels and self.ignore_index is None and target.dtype in (torch.uint8, torch.float32)):
-            return self._hip(input, target)
+            return self._hip(input, target, valid=valid)
         n_classes = input.size(1)
         scores = []
-        for p, t in zip(input, target):
+        for b, (p, t) in enumerate(zip(input, target)):
             if n_classes == 1:
                 pred = (p > 0.5).to(torch.uint8)
             else:
                 pred = torch.zeros_like(p, dtype=torch.uint8).scatter_(0, torch.argmax(p, dim=0, keepdim=True), 1)
             t = t.to(torch.uint8)
+            if valid is not None:
+                keep = (valid[b] != 0).reshape((1,) + tuple(t.shape[1:])).to(torch.uint8)
+                if not bool(keep.any()):
+                    continue
+                pred, t = pred * keep, t * keep
             if self.ignore_index is not None:
                 keep = t != self.ignore_index
                 pred, t = pred * keep, t * keep
             ious = [torch.sum(pred[c] & t[c]).float() / torch.clamp(torch.sum(pred[c] | t[c]).float(), min=1e-8)
                     for c in range(n_classes) if c not in self.skip_channels]
             scores.append(torch.mean(torch.stack(ious)))
+        if not scores:
+            return torch.full((), float("nan"), device=input.device)
         return torch.mean(torch.stack(scores))

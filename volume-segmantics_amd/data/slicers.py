@@ -66,6 +66,38 @@ def imsave_png(path: Union[str, Path], data: np.ndarray) -> None:
     Image.fromarray(np.ascontiguousarray(data)).save(str(path))
 
 
+def clamp_binary_labels(labels: np.ndarray, sparse: bool = False) -> np.ndarray:
+    """The reference's clamp of binary labels to {0, 1} (a copy); with sparse labels the unlabelled value 255 stays."""
+    labels = labels.copy()
+    if sparse:
+        labels[(labels > 1) & (labels != utils.IGNORE_INDEX)] = 1
+    else:
+        labels[labels > 1] = 1
+    return labels
+
+
+def kept_slice_counts(slicer, axis_enum) -> dict:
+    """{axis letter: slices kept} of one slicer's training axes, logged; a volume none of whose slices is kept is an error."""
+    axes = "zyx" if axis_enum == utils.Axis.ALL else axis_enum.name.lower()
+    counts = {axis: int(slicer.labelled_slices(axis).sum()) for axis in axes}
+    shape = dict(zip("zyx", np.asarray(slicer.seg_vol).shape))
+    logging.info("Slices with a labelled voxel, kept for training: " + ", ".join(f"{a}: {counts[a]} of {shape[a]}" for a in axes))
+    if not sum(counts.values()):
+        raise ValueError("no slice of the label volume holds a labelled voxel")
+    return counts
+
+
+def check_ignore_label_occurs(slicers) -> None:
+    """An ``ignore_label`` that is in no label volume of the run is most likely a typo in the settings: refuse it."""
+    slicers = list(slicers)
+    ignore = {s.ignore_label for s in slicers}
+    if len(ignore) != 1:
+        raise ValueError("the slicers of one training run share their ignore_label")
+    ignore = ignore.pop()
+    if ignore is not None and not any(s.ignore_seen for s in slicers):
+        raise ValueError(f"ignore_label {ignore} occurs in no label volume of this run")
+
+
 class TrainingDataSlicer(BaseDataManager):
     """Image pre-processing (BaseDataManager) + slicing of the data and label volumes to PNG files in the xy (z), xz (y) and
     yz (x) planes."""
@@ -86,6 +118,11 @@ class TrainingDataSlicer(BaseDataManager):
         self._preprocess_labels()
 
     def _preprocess_labels(self):
+        self.ignore_label = getattr(self.settings, "ignore_label", None)
+        self.ignore_seen, self._labelled = False, {}
+        if self.ignore_label is not None:
+            self._preprocess_sparse_labels(int(self.ignore_label))
+            return
         seg_classes = np.unique(self.seg_vol)
         self.num_seg_classes = len(seg_classes)
         if self.num_seg_classes > 2:
@@ -102,6 +139,37 @@ class TrainingDataSlicer(BaseDataManager):
         for idx, current in enumerate(seg_classes):
             self.seg_vol[self.seg_vol == current] = idx
 
+    def _preprocess_sparse_labels(self, ignore: int):
+        """Sparse labels (settings key ``ignore_label``): the classes are the distinct values other than ``ignore``, relabelled
+        0 .. K-1 in ascending order; ``ignore`` becomes 255 (base_data_utils.IGNORE_INDEX).  The result is a new uint8 volume, so
+        img_as_ubyte never rescales it, whatever the dtype of the input."""
+        values = np.unique(self.seg_vol)
+        seg_classes = values[values != ignore]
+        self.ignore_seen = len(seg_classes) != len(values)
+        if not len(seg_classes):
+            raise ValueError(f"the label volume holds nothing but the ignore label {ignore}")
+        if len(seg_classes) > 254:
+            raise ValueError(f"{len(seg_classes)} classes and an ignore label: at most 254 classes fit next to the unlabelled "
+                             f"value {utils.IGNORE_INDEX} in uint8 labels")
+        self.num_seg_classes = len(seg_classes)
+        self.multilabel = self.num_seg_classes > 2
+        logging.info(f"Number of classes in segmentation dataset: {self.num_seg_classes} (ignore label {ignore} set aside)")
+        logging.info(f"These classes are: {seg_classes}")
+        relabelled = np.searchsorted(seg_classes, self.seg_vol).astype(np.uint8)     # (the ignore value lands anywhere: overwritten)
+        relabelled[self.seg_vol == ignore] = utils.IGNORE_INDEX
+        self.seg_vol = relabelled
+        self.codes = [f"label_val_{i}" for i in seg_classes]
+
+    def labelled_slices(self, axis: str) -> np.ndarray:
+        """Per slice along ``axis`` ('z', 'y', 'x'): whether it holds a value other than 255.  All true without an ignore label."""
+        n = self.seg_vol.shape["zyx".index(axis)]
+        if self.ignore_label is None:
+            return np.ones(n, dtype=bool)
+        if axis not in self._labelled:
+            others = tuple(a for a in range(3) if a != "zyx".index(axis))
+            self._labelled[axis] = (np.asarray(self.seg_vol) != utils.IGNORE_INDEX).any(axis=others)
+        return self._labelled[axis]
+
     def output_data_slices(self, data_dir: Path, prefix: str) -> None:
         self.data_im_out_dir = Path(data_dir)
         logging.info("Slicing data volume and saving slices to disk")
@@ -116,15 +184,18 @@ class TrainingDataSlicer(BaseDataManager):
 
     def _output_slices_to_disk(self, data_arr, output_path, name_prefix, label=False):
         axis_enum = utils.get_training_axis(self.settings)
+        if self.ignore_label is not None:
+            kept_slice_counts(self, axis_enum)      # logs the slices kept per axis, raises when there is none
         for axis, index in utils.get_axis_index_pairs(data_arr.shape, axis_enum):
+            if self.ignore_label is not None and not self.labelled_slices(axis)[index]:      # sparse labels: a slice without a labelled voxel is left out of the run
+                continue
             self._output_im(utils.axis_index_to_slice(data_arr, axis, index), output_path / f"{name_prefix}_{axis}_stack_{index}", label)
 
     def _output_im(self, data, path, label=False):
         if data.dtype != np.uint8:
             data = img_as_ubyte(data)
         if label and not self.multilabel:
-            data = data.copy()
-            data[data > 1] = 1
+            data = clamp_binary_labels(data, self.ignore_label is not None)
         imsave_png(f"{path}.png", data)
 
     def _delete_image_dir(self, im_dir_path):

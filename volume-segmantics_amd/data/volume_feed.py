@@ -21,7 +21,7 @@ import torch
 
 from ..utilities import base_data_utils as utils
 from .datasets import ShardedBatchSampler, natsort_key, shared_seed
-from .slicers import img_as_ubyte
+from .slicers import check_ignore_label_occurs, clamp_binary_labels, img_as_ubyte, kept_slice_counts
 
 # vs_slice_cut (include/volseg_hip.h), field for field
 CUT_DTYPE = np.dtype([("img_off", "<i8"), ("msk_off", "<i8"), ("row_stride", "<i8"), ("col_stride", "<i8"), ("h", "<i4"), ("w", "<i4"),
@@ -35,12 +35,16 @@ def slice_file_stem(prefix: str, axis: str, index: int) -> str:
     return f"{prefix}_{axis}_stack_{index}"
 
 
-def sample_order(shapes, axis_enum, prefix: str = "data"):
+def sample_order(shapes, axis_enum, prefix: str = "data", keep=None):
     """[(volume, axis letter, index)] in the order the PNG route numbers its samples: VolSeg2dDataset sorts the file names
-    ``<prefix><volume>_<axis>_stack_<index>.png`` with natsort_key, so the same names are built and sorted with the same key here."""
+    ``<prefix><volume>_<axis>_stack_<index>.png`` with natsort_key, so the same names are built and sorted with the same key here.
+    ``keep`` (sparse labels): per volume a function axis letter -> bool per slice (TrainingDataSlicer.labelled_slices); a slice
+    that is not kept has no PNG files and no sample - the names and the order of the others do not change."""
     named = []
     for k, shape in enumerate(shapes):
         for axis, index in utils.get_axis_index_pairs(shape, axis_enum):
+            if keep is not None and not keep[k](axis)[index]:
+                continue
             named.append((natsort_key(slice_file_stem(f"{prefix}{k}", axis, index) + ".png"), k, axis, index))
     named.sort(key=lambda t: t[0])
     return [(k, axis, index) for _key, k, axis, index in named]
@@ -73,8 +77,7 @@ def volumes_as_ubyte(slicer):
     if seg.dtype != np.uint8:
         seg = img_as_ubyte(seg)
     if not slicer.multilabel:
-        seg = seg.copy()
-        seg[seg > 1] = 1
+        seg = clamp_binary_labels(seg, getattr(slicer, "ignore_label", None) is not None)
     return np.ascontiguousarray(data), np.ascontiguousarray(seg)
 
 
@@ -109,6 +112,7 @@ class VolumeSampleTable:
 
     def __init__(self, store: _VolumeStore, samples, image_size: int, descriptors: np.ndarray | None = None):
         self.store, self.samples, self.image_size = store, list(samples), int(image_size)
+        self.ignore_label = None      # 255 when the label volumes are sparse (build_sample_table): left out of the label-range check
         self.descriptors = self._describe() if descriptors is None else descriptors
 
     def __len__(self):
@@ -121,8 +125,10 @@ class VolumeSampleTable:
 
     def subset(self, indices) -> "VolumeSampleTable":
         indices = [int(i) for i in indices]
-        return VolumeSampleTable(self.store, [self.samples[i] for i in indices], self.image_size,
+        part = VolumeSampleTable(self.store, [self.samples[i] for i in indices], self.image_size,
                                  self.descriptors[np.asarray(indices, dtype=np.int64)])
+        part.ignore_label = self.ignore_label
+        return part
 
     def _describe(self) -> np.ndarray:
         d = np.zeros(len(self.samples), dtype=CUT_DTYPE)
@@ -156,7 +162,15 @@ def build_sample_table(slicers, image_size: int) -> VolumeSampleTable:
     if len(axes) != 1:
         raise ValueError("the slicers of one training run share their training_axes")
     store = _VolumeStore([p[0] for p in pairs], [p[1] for p in pairs])
-    return VolumeSampleTable(store, sample_order(store.shapes, axes.pop()), image_size)
+    axis_enum, keep = axes.pop(), None
+    if any(getattr(s, "ignore_label", None) is not None for s in slicers):
+        check_ignore_label_occurs(slicers)
+        for s in slicers:
+            kept_slice_counts(s, axis_enum)
+        keep = [s.labelled_slices for s in slicers]
+    table = VolumeSampleTable(store, sample_order(store.shapes, axis_enum, keep=keep), image_size)
+    table.ignore_label = utils.IGNORE_INDEX if keep is not None else None
+    return table
 
 
 # ---- the cut, in NumPy -----------------------------------------------------------------------------------------------------------
@@ -250,7 +264,8 @@ class VolumeSliceLoader:
         over the source slices could differ.  A few launches per loader, a small chunk at a time."""
         best = -1
         for lo in range(0, len(self.table), _SCAN_CHUNK):
-            best = max(best, int(self._cut(list(range(lo, min(lo + _SCAN_CHUNK, len(self.table)))))[1].max()))
+            masks = self._cut(list(range(lo, min(lo + _SCAN_CHUNK, len(self.table)))))[1]
+            best = max(best, utils.max_real_label(masks, self.table.ignore_label))
         return best
 
     def __len__(self):

@@ -30,7 +30,8 @@ import torch.nn as nn
 from ... import dist as vdist
 from ...checkpoint_compat import reference_pickle_enum
 from ...data.datasets import get_2d_training_dataloaders
-from ...data.losses import BCEDiceLoss, DiceCoefficient, DiceLoss, GeneralizedDiceLoss, HipDiceLoss, HipSegLoss, MeanIoU
+from ...data.losses import (BCEDiceLoss, DiceCoefficient, DiceLoss, GeneralizedDiceLoss, HipDiceLoss, HipSegLoss, MeanIoU,
+                            masked_criterion)
 from ...engine import FusedAdamW, VolSegUnet
 from ...utilities import base_data_utils as utils
 from ...utilities import config as cfg
@@ -54,6 +55,10 @@ class VolSeg2dTrainer:
                 loader.num_labels = self.label_no
         self.codes = labels if isinstance(labels, dict) else {}
         self.settings = settings
+        # sparse labels: the settings key names the unlabelled value of the INPUT volumes; in every batch it is 255 (the slicer
+        # relabels), and the loss and the metric then see a validity mask next to the one-hot targets
+        self.ignore_label = utils.IGNORE_INDEX if getattr(settings, "ignore_label", None) is not None else None
+        self._graph_declined = False
         self.starting_lr, self.end_lr = float(settings.starting_lr), float(settings.end_lr)
         self.log_lr_ratio = self._calculate_log_lr_ratio()
         self.lr_find_epochs = settings.lr_find_epochs
@@ -205,7 +210,16 @@ class VolSeg2dTrainer:
         return es
 
     # ---- the hot loop ---------------------------------------------------------------------------------------
-    def _loss(self, output, targets):
+    def _batch(self, batch, augment_rng=None):
+        """(inputs, targets, valid) of a loader's batch; valid is None without an ignore label"""
+        out = utils.prepare_training_batch(batch, self._device(), self.label_no, augment_rng=augment_rng, ignore_label=self.ignore_label)
+        return out if self.ignore_label is not None else (*out, None)
+
+    def _loss(self, output, targets, valid=None):
+        if valid is not None:
+            if isinstance(self.loss_criterion, (HipDiceLoss, HipSegLoss)):
+                return self.loss_criterion(output, targets, valid)
+            return masked_criterion(self.loss_criterion, output, targets, valid)
         if isinstance(self.loss_criterion, (HipDiceLoss, HipSegLoss)):
             return self.loss_criterion(output, targets)   # reads the uint8 one-hot directly (cross entropy: the position of the 1)
         if self.settings.loss_criterion == "CrossEntropyLoss":
@@ -219,19 +233,24 @@ class VolSeg2dTrainer:
     def _train_one_batch(self, lr_scheduler, batch):
         if self._aug_rng is None:     # draws of the device-side augmentation: one stream per rank
             self._aug_rng = np.random.default_rng([int(getattr(self.settings, "augment_seed", 0)), self.rank])
-        inputs, targets = utils.prepare_training_batch(batch, self._device(), self.label_no, augment_rng=self._aug_rng)
+        inputs, targets, valid = self._batch(batch, self._aug_rng)
         # `step_mode: graph` replays the whole step (zero_grad .. optimizer.step) as recorded hipGraphs - same kernels, same order, same
         # bits, 0.4 ms of host time per step instead of ~1.8; the default enqueues it call by call, which every box of rounds 3 and 4
         # ran 2 - 4 % faster (4.65 vs 4.82 ms; the replay's range boundaries cost more than a host that keeps up) - for a slow or busy
         # host the replay is the one to pick (bench.py times both and keeps the faster)
         fuse = getattr(self.model, "can_fuse_step", None) if getattr(self.settings, "step_mode", "eager") == "graph" else None
+        if fuse is not None and valid is not None:     # the recorded step has no masked form: enqueue call by call
+            if not self._graph_declined:
+                logging.info("step_mode: graph is not available with an ignore_label: the step is enqueued call by call.")
+                self._graph_declined = True
+            fuse = None
         if fuse is not None and isinstance(self.loss_criterion, HipDiceLoss) and fuse(self.optimizer, inputs, targets):
             loss = self.model.fused_train_step(inputs, targets, self.optimizer, eps=self.loss_criterion.epsilon)
             lr_scheduler.step()
             return loss
         self.optimizer.zero_grad()
         output = self.model(inputs)
-        loss = self._loss(output, targets)
+        loss = self._loss(output, targets, valid)
         loss.backward()
         if self.world > 1 and not isinstance(self.model, VolSegUnet):
             vdist.average_gradients(self.model)     # (the engine all-reduces its flat gradient inside backward)
@@ -269,11 +288,16 @@ class VolSeg2dTrainer:
                 for batch in self.validation_loader:
                     if batch is None:      # this rank's share of the last, partial global batch is empty
                         continue
-                    inputs, targets = utils.prepare_training_batch(batch, self._device(), self.label_no)
+                    inputs, targets, valid = self._batch(batch)
                     output = self.model(inputs)
-                    valid_losses.append(self._loss(output, targets).item())
+                    valid_losses.append(self._loss(output, targets, valid).item())
                     metric = getattr(self.eval_metric, "from_logits", None)   # MeanIoU: softmax + metric in one HIP sweep
-                    eval_scores.append(float(metric(output, targets) if metric else self.eval_metric(torch.softmax(output, dim=1), targets)))
+                    if valid is None:
+                        eval_scores.append(float(metric(output, targets) if metric else self.eval_metric(torch.softmax(output, dim=1), targets)))
+                        continue
+                    score = float(metric(output, targets, valid) if metric else self.eval_metric(torch.softmax(output, dim=1), targets, valid))
+                    if not math.isnan(score):      # no sample of the batch has a labelled pixel: not part of the epoch's average
+                        eval_scores.append(score)
             # epoch averages over ALL ranks' batches: every rank holds the same numbers, so the early-stopping decision below
             # is the same everywhere (the reference has one process: np.average over its own lists)
             sums = vdist.allreduce_sums([sum(train_losses), len(train_losses), sum(valid_losses), len(valid_losses),
@@ -390,7 +414,7 @@ class VolSeg2dTrainer:
         if batch is None:
             return
         with torch.no_grad():
-            inputs, targets = utils.prepare_training_batch(batch, self._device(), self.label_no)
+            inputs, targets, _valid = self._batch(batch)
             labels = torch.argmax(torch.softmax(self.model(inputs), dim=1), dim=1)
         try:
             import matplotlib

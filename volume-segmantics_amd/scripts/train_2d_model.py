@@ -17,6 +17,7 @@ import sys
 
 from .. import dist as vdist
 from ..data import TrainingDataSlicer, get_settings_data
+from ..data.slicers import check_ignore_label_occurs
 from ..data.volume_feed import volume_feed_applies
 from ..utilities import arg_parsing
 from ..utilities import base_data_utils as utils
@@ -45,6 +46,7 @@ def main(argv=None) -> None:
     rank, _world = vdist.world()
     data_dir, seg_dir = root / settings.data_im_dirname, root / settings.seg_im_out_dirname
     slicers = [TrainingDataSlicer(d, l, settings) for d, l in zip(data_vols, label_vols)]
+    check_ignore_label_occurs(slicers)
     widest = max(slicers, key=lambda s: s.num_seg_classes)      # (the first of equals, as the reference's loop keeps it)
     max_label_no, label_codes = widest.num_seg_classes, widest.codes
     if feed == "volume":

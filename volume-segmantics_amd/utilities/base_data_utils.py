@@ -124,10 +124,54 @@ def one_hot_encode_array(input_array: np.ndarray, num_labels: int) -> np.ndarray
     return out.reshape((num_labels,) + input_array.shape)
 
 
-def prepare_training_batch(batch, device, num_labels: int, augment_rng=None):
+IGNORE_INDEX = 255      # what "not labelled" is in uint8 label slices, label volumes and masks (the settings key `ignore_label`)
+
+
+def max_real_label(labels, ignore_label=None) -> int:
+    """Largest label of a tensor or array, the unlabelled value left out when ``ignore_label`` is set; -1 when nothing is left."""
+    if ignore_label is not None:
+        labels = labels[labels != ignore_label]
+    count = labels.size if isinstance(labels, np.ndarray) else labels.numel()
+    return int(labels.max()) if count else -1
+
+
+def _prepare_sparse_batch(batch, device, num_labels: int, augment_rng, ignore_label: int):
+    """prepare_training_batch with an ignore label: (inputs, one-hot targets, valid), valid (B, H, W) uint8 = mask != ignore_label;
+    an unlabelled pixel has an all-zero target column."""
+    if ignore_label != IGNORE_INDEX:
+        raise ValueError(f"the unlabelled value of a training batch is {IGNORE_INDEX}, not {ignore_label}")
+    if num_labels > 254:
+        raise ValueError(f"{num_labels} classes and an ignore label: at most 254 classes fit next to the unlabelled value {IGNORE_INDEX}")
+    if not batch[1].is_cuda and max_real_label(batch[1], ignore_label) >= num_labels:
+        raise RuntimeError("Class values must be smaller than num_classes.")
+    inputs = batch[0].to(device, non_blocking=True)
+    masks = batch[1].to(device, non_blocking=True)
+    if inputs.dtype == torch.uint8:
+        if not inputs.is_cuda:
+            raise RuntimeError("raw uint8 training batches are augmented / normalised on the GPU: use augment='host' without one")
+        from ..data.gpu_augment import augment_batch
+        inputs, masks = augment_batch(inputs.reshape(inputs.shape[0], inputs.shape[-2], inputs.shape[-1]), masks.to(torch.uint8), augment_rng)
+    if masks.is_cuda and masks.dtype == torch.uint8:
+        from .._lib import check, lib, ptr, stream_ptr
+        masks = masks.contiguous()
+        n, hw = masks.shape[0], masks[0].numel()
+        targets = torch.empty((n, num_labels) + tuple(masks.shape[1:]), dtype=torch.uint8, device=masks.device)
+        valid = torch.empty_like(masks)
+        check(lib.vs_onehot_valid_u8(ptr(masks), n, num_labels, hw, ignore_label, ptr(targets), ptr(valid), stream_ptr()))
+        return inputs, targets, valid
+    valid = masks != ignore_label
+    index = torch.where(valid, masks, torch.zeros_like(masks)).to(torch.int64)
+    targets = torch.nn.functional.one_hot(index, num_classes=num_labels).permute(0, 3, 1, 2) * valid.unsqueeze(1)
+    return inputs, targets.to(torch.uint8), valid.to(torch.uint8)
+
+
+def prepare_training_batch(batch, device, num_labels: int, augment_rng=None, ignore_label=None):
     """:150-158 - images to the device, masks to one-hot (B,K,H,W) uint8 (built on the device here).  A batch of raw uint8
     images (datasets.VolSeg2dDataset(augment="device")) is augmented - with the reference pipeline's draws from ``augment_rng``,
-    or not at all when it is None - and normalised on the device (data/gpu_augment.py)."""
+    or not at all when it is None - and normalised on the device (data/gpu_augment.py).  ``ignore_label`` (255, sparse labels):
+    a third result, the validity mask (B, H, W) uint8."""
+    if ignore_label is not None:
+        return _prepare_sparse_batch(batch, device, num_labels, augment_rng, int(ignore_label))
     if batch[1].numel() and not batch[1].is_cuda and int(batch[1].max()) >= num_labels:
         # torch.nn.functional.one_hot in the reference raises here (e.g. 0/255 PNG masks with 2 labels); the device kernel
         # would silently give such pixels an all-zero target
