@@ -24,7 +24,7 @@ TOPOLOGIES = {"unet": 0, "unetplusplus": 1, "linknet": 2, "fpn": 3, "deeplabv3pl
 NETWORKS = (("unet", "resnet34"), ("unetplusplus", "resnet34"), ("linknet", "resnet34"), ("fpn", "resnet34"), ("deeplabv3plus", "resnet34"),
             ("deeplabv3", "resnet50"), ("manet", "resnet34"), ("pan", "resnet34"), ("unet", "efficientnet-b3"), ("unet", "timm-resnest50d"),
             ("unet", "resnext50_32x4d"), ("unetplusplus", "efficientnet-b3"))     # (the last: the one with a materialised upsampling, U_UP2)
-N_KINDS = 27          # csrc/unet.hip: enum UnitKind
+N_KINDS = 27          # csrc/unet_plan.h: enum UnitKind
 CLASSES, BATCH = 3, 2
 P, I = C.c_void_p, C.c_int
 

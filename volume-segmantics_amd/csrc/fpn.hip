@@ -5,7 +5,7 @@
 //     same at any integer factor on fp32 NCHW logits   - SegmentationHead(upsampling=4): nn.UpsamplingBilinear2d
 //   * Dropout2d (whole channels of a sample)           - FPNDecoder.dropout, mask drawn from a counter-based generator
 // All HBM-bound sweeps: 16-byte accesses along the channel axis, fixed-order two-stage reductions (no float atomics).  The
-// convolutions between them are conv_igemm / conv_wgrad launches (unet.hip strings them together).
+// convolutions between them are conv_igemm / conv_wgrad launches (unet_plan.hip strings them together: decoder_fpn).
 #include <algorithm>
 
 #include "common.h"
