@@ -117,6 +117,27 @@ int vs_head_wgrad_planes(int dtype, const void* x, const float* dlogits, float* 
                          int h, int wd, void* stream);
 int vs_conv2d_wgrad(const vs_conv_desc* d, const void* src0, const void* src1, const void* dy,
                     float* dw, void* workspace, size_t workspace_bytes, void* stream);
+/* What the weight-gradient launch decides for a descriptor under the current options: the one structure its dispatch switches on.  For
+ * tests and tools.  A grouped layer with fewer than 32 channels per group reports the launch on its 32-channel super-groups, with
+ * extract = 1. */
+typedef struct vs_wgrad_plan {
+    int32_t family;            /* 0 = conv_wgrad_kernel (generic), 1 = conv_wgrad_bf16_kernel (fast), 2 = conv_wgrad_ring_kernel, 3 = row-streaming */
+    int32_t wo;                /* 16-cout fragments per workgroup: WO (generic) / MO (fast, ring); 1 for the row kernels */
+    int32_t taps, stride, pt, dil;   /* template arguments: 9 / 1 taps, stride 1 / 2, 64 * pt pixels per tile (ring: 2, rows: 0), dilation 1 / 2 / 4 */
+    int32_t imgs;              /* ring: images per 128-pixel tile (1: 16 x 8 pixels of one image, 2: two 8 x 8 images); else 0 */
+    int32_t rows_form;         /* rows: 1 = 16 plain channels, 2 = 32 channels behind the nearest upsampling, 3 = fp32 gradient planes; else 0 */
+    int32_t wq;                /* rows: row width / 128; else 0 */
+    int32_t nsplit;            /* K splits = slabs */
+    int32_t tiles_per_split;   /* pixel tiles (rows: row steps) of every split but the last, which may be shorter */
+    int32_t xmode, ppx;        /* workgroup -> (pair, split) assignment of the fast and ring kernels */
+    int32_t reduce_group;      /* -1 = nsplit == 1, the launch writes dw itself; else the slab reduce: 0 = scalar kernel, 1 / 4 / 16 = lane groups
+                                  (the query assumes 16-byte-aligned dw and workspace) */
+    int32_t extract;           /* 1 = the grouped extract runs behind the reduce */
+    uint64_t workspace_bytes;  /* what vs_conv2d_wgrad_workspace answers */
+} vs_wgrad_plan;
+/* Both return exactly the status the launch would return for a sufficient workspace (0, or the refusal with vs_last_error set). */
+int vs_conv2d_wgrad_variant(const vs_conv_desc* d, vs_wgrad_plan* plan);
+int vs_head_wgrad_planes_variant(int dtype, int n, int classes, int h, int wd, vs_wgrad_plan* plan);
 
 /* fp32 master weights [cout][taps][cin] -> copy in `dtype` (wc, same layout; may be NULL) and the flipped / transposed copy
  * [cin][taps reversed][cout] the data gradient reads through vs_conv2d_fwd (wt; may be NULL).  The reference's autograd

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_cases as CC
+import wgrad_cases as WC
 from hip_helpers import (DEV, conv_desc, from_nhwc, lib, rounded, sync, tdtype, to_nhwc, tol, w_krsc)
 
 pytestmark = pytest.mark.gpu
@@ -286,6 +287,14 @@ def test_head_conv_bias_fp32_nchw(code, classes):
     assert torch.allclose(y.cpu(), ref, rtol=1e-4, atol=1e-4 if code == 0 else 2e-2)
 
 
+def _wgrad_figure(L, d, dw, x0, x1, dy):
+    """measured error over the per-element bound of tests/wgrad_cases.py for the weight-gradient launch of d that wrote dw (the plan is
+    the one the library answers for d: these shapes have no row in the table)"""
+    fig = WC.launch_figure(L, d, dw, x0, x1, dy)
+    print(f"weight gradient: {fig:.3g} of the bound")
+    return fig
+
+
 def _prep_weights(L, code, w_oihw):
     cout, cin, k, _ = w_oihw.shape
     wf = w_oihw.permute(0, 2, 3, 1).contiguous().to(DEV)
@@ -328,6 +337,7 @@ def test_dgrad_and_wgrad_match_autograd(code, shape):
     sync()
     ref_dw = wt.grad.permute(0, 2, 3, 1)
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item())
+    assert _wgrad_figure(L, d, dw, x.detach(), None, dy) <= 1.0
     # ---- dgrad = stride-1 conv of the (zero-stuffed) dy with flipped/transposed weights ----
     _, wtr = _prep_weights(L, code, wt.detach())
     dyd = to_nhwc(dy, code)
@@ -388,6 +398,7 @@ def test_grouped_conv_fwd_dgrad_wgrad(code, shape):
     sync()
     ref_dw = wt.grad.permute(0, 2, 3, 1)
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item())
+    assert _wgrad_figure(L, d, dw, x.detach(), None, dy) <= 1.0
     # data gradient: stride-1 grouped conv of the (zero-stuffed) dy with the flipped / transposed copy
     if stride == 2:
         zs = torch.full((n, h, w, c), float("nan"), device=DEV, dtype=tdtype(code))
@@ -516,6 +527,7 @@ def test_grouped_dilated_conv_fwd_dgrad_wgrad(code, shape):
     sync()
     ref_dw = wt.grad.permute(0, 2, 3, 1)
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item())
+    assert _wgrad_figure(L, d, dw, x.detach(), None, dy) <= 1.0
     dx = torch.full((n, h, w, c), float("nan"), device=DEV, dtype=tdtype(code))
     L.check(L.lib.vs_conv2d_fwd(d, L.ptr(dyd), None, L.ptr(wtr), None, None, None, L.ptr(dx), None, None))
     sync()
@@ -569,6 +581,7 @@ def test_conv_transpose_4x4_stride2_as_conv3x3_plus_pixel_shuffle(code, shape):
     sync()
     assert torch.allclose(db.cpu(), bias.grad, rtol=1e-4, atol=1e-4 * bias.grad.abs().max().item())
     assert torch.allclose(dw.cpu(), wt.grad, rtol=1e-3, atol=1e-3 * wt.grad.abs().max().item())
+    assert _wgrad_figure(L, d, dense, x.detach(), None, from_nhwc(dzeff)) <= 1.0          # the 3x3 form's dense gradient, before the gather
     assert torch.allclose(from_nhwc(dx), x.grad, **tol(code, x.grad.abs().max().item()))
     # the shuffle and its inverse are exact permutations
     back = torch.empty_like(zeff)
@@ -606,6 +619,7 @@ def test_dilated_conv_fwd_dgrad_wgrad(code, shape):
     sync()
     ref_dw = wt.grad.permute(0, 2, 3, 1)
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item())
+    assert _wgrad_figure(L, d, dw, x.detach(), None, dy) <= 1.0
     _, wtr = _prep_weights(L, code, wt.detach())
     dd = conv_desc(L, code, n, h, w, cout, cin, 3, 1, 2, dilation=2)
     dx = torch.full((n, h, w, cin), float("nan"), device=DEV, dtype=tdtype(code))
@@ -634,6 +648,7 @@ def test_wgrad_through_upsample_concat_and_split_dgrad(code):
     sync()
     ref_dw = wt.grad.permute(0, 2, 3, 1)
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item())
+    assert _wgrad_figure(L, d, dw, x0.detach(), x1.detach(), dy) <= 1.0
     # dgrad split across the concat: channels < c0 -> full-res "dup" (then 2x2 summed), >= c0 -> dskip
     _, wtr = _prep_weights(L, code, wt.detach())
     dd = conv_desc(L, code, n, h, w, cout, c0 + c1, 3, 1, 1, split_c=c0)

@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_cases as CC
+import wgrad_cases as WC
 from hip_helpers import DEV, conv_desc, from_nhwc, lib, rounded, sync, to_nhwc, tol, w_krsc
 
 pytestmark = pytest.mark.gpu
@@ -337,12 +338,13 @@ def test_ring_weight_gradient_at_32_images(case):
     ref = wt.grad.permute(0, 2, 3, 1)
     d = conv_desc(L, BF, N, h, w, c0, cout, 3, 1, 1, c1=c1, up0=up0)
     x0d, x1d, dyd = to_nhwc(x0, BF), (to_nhwc(x1, BF) if c1 else None), to_nhwc(dy, BF)
-    outs = []
+    outs, plans = [], []
     old = L.lib.vs_get_option(b"wgrad_ring")
     try:
         for ring in (1, 1, 0):
             L.set_option("wgrad_ring", ring)
             ws_bytes = L.lib.vs_conv2d_wgrad_workspace(d)
+            plans.append(WC.queried_plan(L, d))
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
             dw = torch.full((cout, 3, 3, c0 + c1), float("nan"), device=DEV)
             L.check(L.lib.vs_conv2d_wgrad(d, _ptr(x0d), _ptr(x1d), _ptr(dyd), _ptr(dw), _ptr(ws), ws_bytes, None))
@@ -354,6 +356,11 @@ def test_ring_weight_gradient_at_32_images(case):
     scale = ref.abs().max().item()
     assert torch.isfinite(base).all()
     assert torch.allclose(base.cpu(), ref, rtol=1e-3, atol=1e-3 * scale), (base.cpu() - ref).abs().max()
+    assert plans[0].family == WC.RING and plans[2].family == WC.FAST
+    for i in (0, 2):        # the ring kernel and the register-staged one, each against the bound of its own plan
+        fig = WC.launch_figure(L, d, outs[i], x0, x1, dy, plans[i])
+        print(f"weight gradient ({WC.FAMILY[plans[i].family]}): {fig:.3g} of the bound")
+        assert fig <= 1.0, fig
     assert torch.equal(outs[1], base)
     assert torch.allclose(outs[2], base, rtol=1e-5, atol=1e-5 * scale), (outs[2] - base).abs().max()
 
@@ -391,6 +398,9 @@ def test_row_streaming_weight_gradient_of_the_full_resolution_layers(case):
     scale = ref.abs().max().item()
     assert torch.isfinite(outs[0]).all()
     assert torch.allclose(outs[0].cpu(), ref, rtol=1e-3, atol=1e-3 * scale), (outs[0].cpu() - ref).abs().max()
+    fig = WC.launch_figure(L, d, outs[0], x, None, dy)
+    print(f"weight gradient: {fig:.3g} of the bound")
+    assert fig <= 1.0, fig
     assert torch.equal(outs[0], outs[1])
 
 
@@ -425,4 +435,10 @@ def test_head_backward_from_the_loss_gradient_planes(case):
     assert torch.isfinite(dx.float()).all() and torch.isfinite(dw).all()
     assert torch.allclose(from_nhwc(dx), ref_dx, **tol(BF, ref_dx.abs().max().item())), (from_nhwc(dx) - ref_dx).abs().max()
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item()), (dw.cpu() - ref_dw).abs().max()
+    pl = L.WgradPlan()
+    L.check(L.lib.vs_head_wgrad_planes_variant(BF, n, k, h, w, pl))
+    ref64, bound = WC.reference_and_bound(BF, x.detach(), None, rounded(dl, BF), WC.plan_of(pl), pad=1)
+    fig = WC.figure_against(dw.cpu().reshape(ref64.shape), ref64, bound)
+    print(f"weight gradient: {fig:.3g} of the bound")
+    assert fig <= 1.0, fig
     assert torch.equal(outs[1][0], dx) and torch.equal(outs[1][1], dw)

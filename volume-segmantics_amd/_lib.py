@@ -48,6 +48,12 @@ class ConvTrain(C.Structure):
                 ("nl_gamma", C.c_void_p), ("nl_beta", C.c_void_p), ("nl_y", C.c_void_p)]
 
 
+class WgradPlan(C.Structure):
+    """vs_wgrad_plan: what the weight-gradient launch decides for a descriptor (vs_conv2d_wgrad_variant)"""
+    _fields_ = [(n, C.c_int32) for n in ("family", "wo", "taps", "stride", "pt", "dil", "imgs", "rows_form", "wq", "nsplit", "tiles_per_split",
+                                         "xmode", "ppx", "reduce_group", "extract")] + [("workspace_bytes", C.c_uint64)]
+
+
 class DirMap(C.Structure):
     _fields_ = [("base", C.c_int64), ("ss", C.c_int64), ("sh", C.c_int64), ("sw", C.c_int64)] + [
         (n, C.c_int32) for n in ("depth", "h", "w", "hp", "wp", "pad_top", "pad_left", "crop_top", "crop_left")]
@@ -79,6 +85,8 @@ _SIGS = {
     "vs_conv2d_pair_fwd": (I, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "vs_conv2d_wgrad_workspace": (SZ, [C.POINTER(ConvDesc)]),
     "vs_conv2d_wgrad": (I, [C.POINTER(ConvDesc), P, P, P, P, P, SZ, P]),
+    "vs_conv2d_wgrad_variant": (I, [C.POINTER(ConvDesc), C.POINTER(WgradPlan)]),
+    "vs_head_wgrad_planes_variant": (I, [I, I, I, I, I, C.POINTER(WgradPlan)]),
     "vs_head_dgrad_planes": (I, [I, P, P, P, I, I, I, I, I, P]),
     "vs_head_wgrad_planes_workspace": (SZ, [I, I, I, I, I]),
     "vs_head_wgrad_planes": (I, [I, P, P, P, P, SZ, I, I, I, I, P]),

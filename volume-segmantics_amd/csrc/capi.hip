@@ -164,6 +164,15 @@ extern "C" size_t vs_conv2d_wgrad_workspace(const vs_conv_desc* d) {
     return wgrad_workspace_bytes(d->dtype, p);
 }
 
+// what vs_conv2d_wgrad decides for this descriptor, and its status (for tests and tools)
+extern "C" int vs_conv2d_wgrad_variant(const vs_conv_desc* d, vs_wgrad_plan* plan) {
+    WgradParams p;
+    int rc = desc_to_wgrad(d, p);
+    if (rc) return rc;
+    VS_REQUIRE(plan, "conv_wgrad_variant: null plan");
+    return conv_wgrad_plan(d->dtype, p, plan);
+}
+
 extern "C" int vs_conv2d_wgrad(const vs_conv_desc* d, const void* src0, const void* src1, const void* dy, float* dw,
                                void* workspace, size_t workspace_bytes, void* stream) {
     WgradParams p;
@@ -194,6 +203,12 @@ static WgradParams head_wgrad_params(int n, int classes, int h, int wd) {
 extern "C" size_t vs_head_wgrad_planes_workspace(int dtype, int n, int classes, int h, int wd) {
     const WgradParams p = head_wgrad_params(n, classes, h, wd);
     return conv_wgrad_takes_planes(dtype, p) ? wgrad_workspace_bytes(dtype, p) : 0;
+}
+extern "C" int vs_head_wgrad_planes_variant(int dtype, int n, int classes, int h, int wd, vs_wgrad_plan* plan) {
+    VS_REQUIRE(plan, "head_wgrad_planes_variant: null plan");
+    const WgradParams p = head_wgrad_params(n, classes, h, wd);
+    if (!conv_wgrad_takes_planes(dtype, p)) { vs_set_error("head_wgrad_planes: unsupported shape"); return VS_ERR_UNSUPPORTED; }
+    return conv_wgrad_plan(dtype, p, plan);
 }
 extern "C" int vs_head_wgrad_planes(int dtype, const void* x, const float* dlogits, float* dw, void* workspace, size_t workspace_bytes, int n, int classes,
                                     int h, int wd, void* stream) {

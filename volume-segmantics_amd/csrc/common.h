@@ -358,6 +358,9 @@ bool conv_wgrad_honours_cout_live(int dtype, const WgradParams& p);
 bool conv_wgrad_takes_planes(int dtype, const WgradParams& p);   // (ask with dy_planes = the class count)
 size_t wgrad_workspace_bytes(int dtype, const WgradParams& p);
 int launch_conv_wgrad(int dtype, const WgradParams& p, hipStream_t s);
+// what launch_conv_wgrad decides for p under the current options, and the status it would return for a sufficient workspace (host only;
+// null dw / partials count as 16-byte aligned)
+int conv_wgrad_plan(int dtype, const WgradParams& p, vs_wgrad_plan* plan);
 // dw[i] = sum_k partials[k*n + i], fixed summation order
 int launch_slab_reduce(const float* partials, float* dw, size_t n, int nparts, hipStream_t s);
 // the lane-group count G of the slab_reduce4_kernel<G> launch_slab_reduce picks for (n, nparts) - 1, 4 or 16 - or 0 when it takes the

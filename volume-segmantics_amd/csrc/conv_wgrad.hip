@@ -95,6 +95,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p, WGeom g)
         dseg[i] = item % SEGS;
     }
     uint4 preg[PITEMS], dreg[DITEMS];
+    const bool dy16 = p.Cout % EPS == 0;                  // dy pixel rows are whole 16-byte segments
     auto load_tile = [&](int tile) {
         int b = tile;
         const int tx = b % g.tiles_w; b /= g.tiles_w;
@@ -118,8 +119,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradParams p, WGeom g)
             const int co = co0 + dseg[i] * EPS;
             if (ho < p.Hout && wo_ < p.Wout && co < p.Cout) {
                 const T* sp = (const T*)p.dy + (((size_t)n * p.Hout + ho) * p.Wout + wo_) * p.Cout + co;
-                if (co + EPS <= p.Cout) dreg[i] = *reinterpret_cast<const uint4*>(sp);
-                else {  // ragged channel tail
+                if (dy16 && co + EPS <= p.Cout) dreg[i] = *reinterpret_cast<const uint4*>(sp);
+                else {  // ragged channel tail; every segment of a pixel row that is no multiple of 16 bytes (sp is not 16-byte aligned then)
                     alignas(16) T tmp[EPS];
                     for (int e = 0; e < EPS; ++e) tmp[e] = (co + e < p.Cout) ? sp[e] : (T)0;
                     dreg[i] = *reinterpret_cast<const uint4*>(tmp);
@@ -475,6 +476,8 @@ int geom(const WgradParams& p, WGeom& g, int& WO) {
     VS_REQUIRE(Cin % EPS == 0 && p.C0 % EPS == 0, "conv_wgrad: channel counts must be multiples of %d", EPS);
     VS_REQUIRE(p.C1 == 0 || p.C0 % CK == 0, "conv_wgrad: concat boundary must be a multiple of %d", CK);
     VS_REQUIRE((p.KH == 3 && p.KW == 3) || (p.KH == 1 && p.KW == 1), "conv_wgrad: only 3x3 and 1x1 kernels");
+    // (the kernels address the source as hi >> up0: a zero-stuffed source, up0 = 2, would be read as a x4 nearest upsampling)
+    VS_REQUIRE(p.up0 == 0 || p.up0 == 1, "conv_wgrad: the source is plain or nearest-upsampled x2 (up0 0 / 1), not up0 = %d", p.up0);
     // tile: 16x8 pixels (PT = 2) for stride-1 layers at least 16 wide, else 64 pixels (8x8; stride 2: 16x4 when wide enough)
     const int PT = (p.stride == 1 && p.Wout >= 16 && p.Hout * p.Wout >= 128 && p.dil < 4) ? 2 : 1;
     g.tw_shift = p.stride == 1 ? (PT == 2 ? 4 : 3) : (p.Wout >= 16 ? 4 : 3);
@@ -576,6 +579,59 @@ int geom(const WgradParams& p, WGeom& g, int& WO) {
     return VS_OK;
 }
 
+// The one decision of the weight-gradient launch (host only): geom(), then the kernel instantiation dispatch() will run, as the
+// plain structure vs_conv2d_wgrad_variant hands out.  Every refusal of the launch but the workspace size is made here.
+int wgrad_unbuilt(const char* what) {
+    vs_set_error("conv_wgrad: %s", what);
+    return VS_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int wgrad_plan(const WgradParams& p, WGeom& g, vs_wgrad_plan& pl) {
+    pl = vs_wgrad_plan{};
+    const bool extract = p.cg && p.cg < 32;          // the super-group slabs are denser than dw: one more slab, then the gather
+    const int nt = p.KH * p.KW;
+    const size_t slab = (size_t)p.Cout * nt * (p.cg ? 32 : p.C0 + p.C1) * sizeof(float);
+    if (extract) {
+        WgradParams q = p;
+        q.cg = 32;                                    // as a grouped layer whose groups ARE the super-groups
+        WGeom gq; int woq;
+        if (int rc = geom<T>(p, gq, woq)) return rc;   // (the same geometry: geom() asks only whether the layer is grouped)
+        q.dw = p.partials ? p.partials + (size_t)gq.nsplit * (slab / sizeof(float)) : nullptr;
+        if (int rc = wgrad_plan<T>(q, g, pl)) return rc;
+        pl.extract = 1;
+        pl.workspace_bytes = ((size_t)pl.nsplit + 1) * slab;
+        return VS_OK;
+    }
+    int WO;
+    if (int rc = geom<T>(p, g, WO)) return rc;
+    VS_REQUIRE(!p.dy_planes || (sizeof(T) == 2 && g.rows == 1), "conv_wgrad: this launch cannot read gradient planes (ask conv_wgrad_takes_planes)");
+    const int dil = p.dil > 1 ? p.dil : 1;
+    pl.wo = WO; pl.taps = nt; pl.stride = p.stride == 2 ? 2 : 1; pl.dil = dil;
+    pl.pt = (p.stride == 2 || dil == 4) ? 1 : g.PT;
+    pl.nsplit = g.nsplit; pl.xmode = g.xmode; pl.ppx = g.ppx;
+    pl.tiles_per_split = cdiv(g.total_tiles, g.nsplit);
+    pl.workspace_bytes = (size_t)g.nsplit * slab;
+    size_t n = slab / sizeof(float);                  // outputs the slab reduce sums
+    if (sizeof(T) == 2 && g.rows) {
+        const bool planes = g.rows == 1 && p.dy_planes > 0;
+        VS_REQUIRE(!p.dy_planes || (planes && p.dy_planes <= 7 && p.cout_live == p.dy_planes), "conv_wgrad: gradient planes are taken by the 16-channel row kernel only (<= 7 of them)");
+        pl.family = 3; pl.pt = 0;
+        pl.rows_form = g.rows == 2 ? 2 : (planes ? 3 : 1);
+        pl.wq = p.Wout / 128;
+        pl.tiles_per_split = g.rows_per;
+        n = (size_t)(g.rows == 1 && p.cout_live > 0 && p.cout_live < 16 ? p.cout_live : 16) * 9 * p.C0;
+    } else if (sizeof(T) == 2 && g.fast && dil == 1 && (g.ring == 1 || (g.ring == 2 && WO == 4))) {
+        pl.family = 2; pl.pt = 2; pl.imgs = g.ring;
+    } else {
+        pl.family = sizeof(T) == 2 && g.fast ? 1 : 0;
+        if (dil > 1 && WO == 1) return wgrad_unbuilt("the dilated kernels are built for 32 output channels or more");
+        VS_REQUIRE(g.PH * g.PW * 4 <= wg_patch_items(pl.pt, dil > 1 ? 2 : pl.stride) * 256, "conv_wgrad: patch exceeds the staging budget");
+    }
+    pl.reduce_group = g.nsplit == 1 ? -1 : slab_reduce_groups(p.partials, p.dw, n, g.nsplit);
+    return VS_OK;
+}
+
 template <int MO, int NTAPS, int STRIDE, int PT, int DIL = 1>
 int launch_fast(const WgradParams& p, const WGeom& g, hipStream_t s) {
     static bool attr_set = false;
@@ -666,73 +722,60 @@ int launch_one(const WgradParams& p, const WGeom& g, hipStream_t s) {
 
 template <typename T>
 int dispatch(const WgradParams& p, hipStream_t s) {
-    WGeom g; int WO;
-    int rc = geom<T>(p, g, WO);
-    if (rc) return rc;
-    const size_t slab = (size_t)p.Cout * p.KH * p.KW * (p.cg ? 32 : p.C0 + p.C1) * sizeof(float);
-    const bool extract = p.cg && p.cg < 32;          // the super-group slabs are denser than dw: one more slab, then the gather
-    const size_t need = ((size_t)g.nsplit + (extract ? 1 : 0)) * slab;
-    VS_REQUIRE(p.partials && p.partial_bytes >= need, "conv_wgrad: workspace %zu < %zu", p.partial_bytes, need);
-    const int nt = p.KH * p.KW;
-    if (extract) {
+    WGeom g; vs_wgrad_plan pl;
+    if (int rc = wgrad_plan<T>(p, g, pl)) return rc;
+    VS_REQUIRE(p.partials && p.partial_bytes >= pl.workspace_bytes, "conv_wgrad: workspace %zu < %zu", p.partial_bytes, (size_t)pl.workspace_bytes);
+    if (pl.extract) {
         WgradParams q = p;
         q.cg = 32;                                    // as a grouped layer whose groups ARE the super-groups ...
-        q.dw = p.partials + (size_t)g.nsplit * (slab / sizeof(float));
+        q.dw = p.partials + (size_t)pl.nsplit * p.Cout * pl.taps * 32;
         const int rc2 = dispatch<T>(q, s);
         if (rc2) return rc2;
-        const int n = p.Cout * nt * p.cg;             // ... then every group's cg x cg block out of its 32 x 32 slab
-        hipLaunchKernelGGL(wgrad_group_extract_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, q.dw, p.dw, n, nt, p.cg);
+        const int n = p.Cout * pl.taps * p.cg;        // ... then every group's cg x cg block out of its 32 x 32 slab
+        hipLaunchKernelGGL(wgrad_group_extract_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, q.dw, p.dw, n, pl.taps, p.cg);
         VS_LAUNCH_CHECK();
         return VS_OK;
     }
-    VS_REQUIRE(!p.dy_planes || (sizeof(T) == 2 && g.rows == 1), "conv_wgrad: this launch cannot read gradient planes (ask conv_wgrad_takes_planes)");
+    const int key = pl.wo * 1000 + pl.taps * 100 + pl.stride * 10 + pl.pt;      // (dilated: the 3x3 stride-1 forms only)
     if constexpr (sizeof(T) == 2) {
-        if (g.rows) return p.Wout == 128 ? launch_rows_wgrad<1>(p, g, s) : (p.Wout == 256 ? launch_rows_wgrad<2>(p, g, s) : launch_rows_wgrad<4>(p, g, s));
-        if (g.fast) {
-            if (p.dil == 2) {   // the dilated 3x3 layers (>= 32 channels): 64-pixel and 128-pixel tiles
-                if (WO == 4) return g.PT == 2 ? launch_fast<4, 9, 1, 2, 2>(p, g, s) : launch_fast<4, 9, 1, 1, 2>(p, g, s);
-                if (WO == 2) return g.PT == 2 ? launch_fast<2, 9, 1, 2, 2>(p, g, s) : launch_fast<2, 9, 1, 1, 2>(p, g, s);
-                return VS_ERR_UNSUPPORTED;
+        if (pl.family == 3) return pl.wq == 1 ? launch_rows_wgrad<1>(p, g, s) : (pl.wq == 2 ? launch_rows_wgrad<2>(p, g, s) : launch_rows_wgrad<4>(p, g, s));
+        if (pl.family == 2) {
+            if (pl.imgs == 2) return launch_ring_wgrad<4, 3, 2>(p, g, s);   // two 8 x 8 images per tile
+            if (pl.wo == 4) return launch_ring_wgrad<4, 4, 1>(p, g, s);      // 16 x 8 tiles
+            return pl.wo == 2 ? launch_ring_wgrad<2, 4, 1>(p, g, s) : launch_ring_wgrad<1, 4, 1>(p, g, s);
+        }
+        if (pl.family == 1) {
+            if (pl.dil == 2) {   // the dilated 3x3 layers (>= 32 channels): 64-pixel and 128-pixel tiles
+                if (pl.wo == 4) return pl.pt == 2 ? launch_fast<4, 9, 1, 2, 2>(p, g, s) : launch_fast<4, 9, 1, 1, 2>(p, g, s);
+                return pl.pt == 2 ? launch_fast<2, 9, 1, 2, 2>(p, g, s) : launch_fast<2, 9, 1, 1, 2>(p, g, s);
             }
-            if (p.dil == 4) {   // (64-pixel tiles only: the 128-pixel tile's 24 x 16 patch exceeds the staging budget)
-                if (WO == 4) return launch_fast<4, 9, 1, 1, 4>(p, g, s);
-                if (WO == 2) return launch_fast<2, 9, 1, 1, 4>(p, g, s);
-                return VS_ERR_UNSUPPORTED;
-            }
-            if (g.ring == 1) {        // 16 x 8 tiles
-                if (WO == 4) return launch_ring_wgrad<4, 4, 1>(p, g, s);
-                if (WO == 2) return launch_ring_wgrad<2, 4, 1>(p, g, s);
-                if (WO == 1) return launch_ring_wgrad<1, 4, 1>(p, g, s);
-            }
-            if (g.ring == 2 && WO == 4) return launch_ring_wgrad<4, 3, 2>(p, g, s);   // two 8 x 8 images per tile
-#define VS_WGF_CASE(mo, t)                                                                \
-    if (WO == mo && nt == t) {                                                            \
-        if (p.stride == 2) return launch_fast<mo, t, 2, 1>(p, g, s);                      \
-        return g.PT == 2 ? launch_fast<mo, t, 1, 2>(p, g, s) : launch_fast<mo, t, 1, 1>(p, g, s); \
-    }
-            VS_WGF_CASE(4, 9) VS_WGF_CASE(2, 9) VS_WGF_CASE(1, 9) VS_WGF_CASE(4, 1) VS_WGF_CASE(2, 1) VS_WGF_CASE(1, 1)
+            if (pl.dil == 4)     // (64-pixel tiles only: the 128-pixel tile's 24 x 16 patch exceeds the staging budget)
+                return pl.wo == 4 ? launch_fast<4, 9, 1, 1, 4>(p, g, s) : launch_fast<2, 9, 1, 1, 4>(p, g, s);
+            switch (key) {
+#define VS_WGF_CASE(mo, t)                                                  \
+    case mo * 1000 + t * 100 + 21: return launch_fast<mo, t, 2, 1>(p, g, s); \
+    case mo * 1000 + t * 100 + 12: return launch_fast<mo, t, 1, 2>(p, g, s); \
+    case mo * 1000 + t * 100 + 11: return launch_fast<mo, t, 1, 1>(p, g, s);
+                VS_WGF_CASE(4, 9) VS_WGF_CASE(2, 9) VS_WGF_CASE(1, 9) VS_WGF_CASE(4, 1) VS_WGF_CASE(2, 1) VS_WGF_CASE(1, 1)
 #undef VS_WGF_CASE
-            return VS_ERR_UNSUPPORTED;
+            }
+            return wgrad_unbuilt("no fast kernel for this plan");
         }
     }
-    if (p.dil == 2) {
-        if (WO == 4) return g.PT == 2 ? launch_one<T, 4, 9, 1, 2, 2>(p, g, s) : launch_one<T, 4, 9, 1, 1, 2>(p, g, s);
-        if (WO == 2) return g.PT == 2 ? launch_one<T, 2, 9, 1, 2, 2>(p, g, s) : launch_one<T, 2, 9, 1, 1, 2>(p, g, s);
-        return VS_ERR_UNSUPPORTED;
+    if (pl.dil == 2) {
+        if (pl.wo == 4) return pl.pt == 2 ? launch_one<T, 4, 9, 1, 2, 2>(p, g, s) : launch_one<T, 4, 9, 1, 1, 2>(p, g, s);
+        return pl.pt == 2 ? launch_one<T, 2, 9, 1, 2, 2>(p, g, s) : launch_one<T, 2, 9, 1, 1, 2>(p, g, s);
     }
-    if (p.dil == 4) {
-        if (WO == 4) return launch_one<T, 4, 9, 1, 1, 4>(p, g, s);
-        if (WO == 2) return launch_one<T, 2, 9, 1, 1, 4>(p, g, s);
-        return VS_ERR_UNSUPPORTED;
-    }
-#define VS_WG_CASE(wo, t)                                                                  \
-    if (WO == wo && nt == t) {                                                             \
-        if (p.stride == 2) return launch_one<T, wo, t, 2, 1>(p, g, s);                     \
-        return g.PT == 2 ? launch_one<T, wo, t, 1, 2>(p, g, s) : launch_one<T, wo, t, 1, 1>(p, g, s); \
-    }
-    VS_WG_CASE(4, 9) VS_WG_CASE(2, 9) VS_WG_CASE(1, 9) VS_WG_CASE(4, 1) VS_WG_CASE(2, 1) VS_WG_CASE(1, 1)
+    if (pl.dil == 4) return pl.wo == 4 ? launch_one<T, 4, 9, 1, 1, 4>(p, g, s) : launch_one<T, 2, 9, 1, 1, 4>(p, g, s);
+    switch (key) {
+#define VS_WG_CASE(wo, t)                                                     \
+    case wo * 1000 + t * 100 + 21: return launch_one<T, wo, t, 2, 1>(p, g, s); \
+    case wo * 1000 + t * 100 + 12: return launch_one<T, wo, t, 1, 2>(p, g, s); \
+    case wo * 1000 + t * 100 + 11: return launch_one<T, wo, t, 1, 1>(p, g, s);
+        VS_WG_CASE(4, 9) VS_WG_CASE(2, 9) VS_WG_CASE(1, 9) VS_WG_CASE(4, 1) VS_WG_CASE(2, 1) VS_WG_CASE(1, 1)
 #undef VS_WG_CASE
-    return VS_ERR_UNSUPPORTED;
+    }
+    return wgrad_unbuilt("no kernel for this plan");
 }
 
 }  // namespace
@@ -771,6 +814,14 @@ int launch_slab_reduce(const float* partials, float* dw, size_t n, int nparts, h
 bool conv_wgrad_takes_planes(int dtype, const WgradParams& p) {
     WGeom g; int WO;
     return dtype == VS_BF16 && p.dy_planes >= 1 && p.dy_planes <= 7 && geom<bf16_t>(p, g, WO) == VS_OK && g.rows == 1;
+}
+
+int conv_wgrad_plan(int dtype, const WgradParams& p, vs_wgrad_plan* plan) {
+    WGeom g;
+    if (dtype == VS_BF16) return wgrad_plan<bf16_t>(p, g, *plan);
+    if (dtype == VS_F32) return wgrad_plan<float>(p, g, *plan);
+    vs_set_error("conv_wgrad: bad dtype %d", dtype);
+    return VS_ERR_INVALID;
 }
 
 bool conv_wgrad_honours_cout_live(int dtype, const WgradParams& p) {
