@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """What the network passes compute, digested - the device-side companion of unet_plan_sweep.py.  Needs a GPU.
 
-    python tools/pass_digest_sweep.py LIB [--out FILE]
+    python tools/pass_digest_sweep.py LIB [--out FILE] [--option NAME=VALUE]...
     python tools/pass_digest_sweep.py LIB --kinds          (host only: which unit kinds the listed networks reach)
 
-LIB is a libvolseg_hip.so.  For each network of NETWORKS, with seeded parameters, input and dropout draws (vs_unet_set_rng): one
+LIB is a libvolseg_hip.so; --option sets a runtime option of it (vs_set_option) before anything runs.  For each network of NETWORKS, with seeded parameters, input and dropout draws (vs_unet_set_rng): one
 evaluation forward (bf16) and, in fp32 and in bf16, two fused training steps (vs_unet_forward in training mode +
 vs_unet_backward_adamw; the first with the encoder frozen, the second without).  Batch 2 at 64 x 64 (128 x 128 under the dilating
 decoders).  One line per network and precision with the SHA-256 of the evaluation logits, of both steps' training logits, of both
@@ -38,7 +38,7 @@ def load(path):
             ("vs_unet_param_elems_ex", C.c_int64, [I, I]), ("vs_unet_bnstate_elems_ex", C.c_int64, [I, I]),
             ("vs_unet_workspace_bytes", C.c_size_t, [P, I]), ("vs_unet_prepare", I, [P, P, P, I, P, P]),
             ("vs_unet_forward", I, [P, P, P, P, I, I, P, P, P]), ("vs_unet_backward_adamw", I, [P, P, P, I, I, P, P, P, P]),
-            ("vs_unet_set_rng", I, [P, C.c_uint32, P])):
+            ("vs_unet_set_rng", I, [P, C.c_uint32, P]), ("vs_set_option", I, [C.c_char_p, I])):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
     return lib
@@ -158,9 +158,20 @@ def main():
     kinds_only = "--kinds" in args
     if kinds_only:
         args.remove("--kinds")
+    options = []
+    while "--option" in args:
+        i = args.index("--option")
+        name, _, value = args[i + 1].partition("=") if i + 1 < len(args) else ("", "", "")
+        if not name or not value.lstrip("-").isdigit():
+            sys.exit(__doc__)
+        options.append((name, int(value)))
+        del args[i:i + 2]
     if len(args) != 1:
         sys.exit(__doc__)
     lib = load(args[0])
+    for name, value in options:
+        if lib.vs_set_option(name.encode(), value):
+            sys.exit(f"vs_set_option({name}) failed: {lib.vs_last_error().decode()}")
     kinds = kinds_reached(lib)
     missing = sorted(set(range(N_KINDS)) - kinds)
     assert not missing, f"the listed networks never reach the unit kinds {missing}"

@@ -324,7 +324,6 @@ int launch_bn_finalize_partials(const float* partial, int nparts, int c, int64_t
                                 float* mean, float* invstd, float* running_mean, float* running_var, hipStream_t s);
 // train-mode BatchNorm whose sums sit in fixed-point bins (ConvParams::stats_bins): finalise the nb rows inline, normalise
 constexpr double kStatScale1 = 16777216.0, kStatScale2 = 65536.0;     // 2^24, 2^16
-constexpr double kBwdStatScale = 68719476736.0;                        // 2^36: gradient sums (|sum| < 1.3e8, resolution 1.5e-11)
 int launch_bn_apply_from_bins(int dtype, const void* x, const unsigned long long* bins, int nb, float eps, float momentum, float* mean,
                               float* invstd, float* running_mean, float* running_var, const float* gamma, const float* beta,
                               const void* residual, int relu, void* y, int64_t rows, int c, hipStream_t s, int64_t stat_rows = 0);
@@ -332,11 +331,10 @@ int launch_zero_u64(unsigned long long* p, size_t n, hipStream_t s);
 bool stem_fwd_bins_ok(int dtype);
 int launch_stem_fwd_bins(const float* x, const float* w, void* z, int n, int h, int w_, unsigned long long* bins, int nb, hipStream_t s);
 
-// BatchNorm backward (dx, dres, dgamma, dbeta): three launches, or ONE with a grid barrier for tensors of a few MB (norm.hip).
-// ctl: 16 zeroed bytes of barrier counters that re-arm themselves (null: the end of `workspace`, zeroed by a memset first)
+// BatchNorm backward (dx, dres, dgamma, dbeta) in three launches: partial sums, finalise, apply (norm.hip)
 int bn_bwd_dispatch(int dtype, const void* dy, const void* y, const void* x, const float* mean, const float* invstd, const float* gamma,
                     const float* beta, int relu, void* dx, void* dres, float* dgamma, float* dbeta, int64_t rows, int c, float* workspace,
-                    size_t workspace_bytes, unsigned* ctl, hipStream_t s, const BnSync* sync = nullptr);
+                    size_t workspace_bytes, hipStream_t s, const BnSync* sync = nullptr);
 
 int launch_upsample2x_bwd(int dtype, const void* dy, void* dx, int n, int h, int w, int c, int accumulate, hipStream_t stream);
 

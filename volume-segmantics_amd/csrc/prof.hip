@@ -87,7 +87,7 @@ Opt g_opts[] = {
     {"wgrad_target", 96, false}, {"wgrad_target_plain", 256, false}, {"wgrad_slab_mb", 16, false}, {"fork_every", 2, false},
     {"bn_inline_rows", 64, false}, {"nl_max_c", 64, false},
     // forms of the BatchNorm sweeps (norm.hip): 1 = the first trip's row and parameter loads are issued before the statistics prologue,
-    // 0 = the forms without it (same bits: tests/test_hip_bn_prefetch.py)
+    // 0 = the same sweeps without the early loads, every trip loaded inside the row loop (same bits: tests/test_hip_bn_prefetch.py)
     {"bn_prefetch", 1, false}};
 }
 int vs_option(const char* name) {

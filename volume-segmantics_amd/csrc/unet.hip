@@ -371,7 +371,7 @@ int train_norm_bwd(const Ctx& c, const Unit& u, Bwd& b) {
     ProfScope prof(PK_BN_BWD, 0, act_bytes(c, u, ((u.relu && !recompute_mask) ? 6 : 4) + 1 + (dres ? 1 : 0)), c.s);
     return bn_bwd_dispatch(dt, c.da(u.out), recompute_mask ? nullptr : c.a(u.out), c.z(u.out), c.bnc(u, 2), c.bnc(u, 3), c.P(u.bn_idx),
                            c.P(u.bn_idx + 1), u.relu, c.dz(u.out), dres, b.grad(c, u.bn_idx), b.grad(c, u.bn_idx + 1), c.rows(u), u.cout, c.bnws(),
-                           net->bnws_bytes, (unsigned*)(c.ws + net->off_bncnt), c.s, sync);
+                           net->bnws_bytes, c.s, sync);
 }
 
 // The head's data gradient reads dLoss / dlogits straight from its planes where head_dgrad_planes_kernel applies; the 16-channel NHWC
@@ -1431,7 +1431,7 @@ extern "C" int vs_unet_prepare(vs_unet_t* net, const float* params, const float*
     VS_REQUIRE(net && params && bnstate && workspace, "unet_prepare: null pointer");
     Ctx c{net, (char*)workspace, params, const_cast<float*>(bnstate), (hipStream_t)stream, 0};
     ProfScope prof(PK_PREPARE, 0, (double)net->layout.n_params * (4 + net->esz * (training ? 2 : 1)), c.s);
-    VS_CHECK_HIP(hipMemsetAsync(c.ws + net->off_bncnt, 0, 256, c.s));   // (the counters re-arm themselves; this covers a fresh workspace)
+    VS_CHECK_HIP(hipMemsetAsync(c.ws + net->off_bncnt, 0, 256, c.s));   // (reserved, unused bytes of the plan: see unet_plan.h)
     {   // every conv layer's low-precision copy and flipped/transposed dgrad copy in one launch
         WeightCopyRow rows[64];
         int nl = 0;

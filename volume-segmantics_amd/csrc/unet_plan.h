@@ -94,7 +94,8 @@ struct vs_unet {
     size_t off_bins0 = 0, bins_bytes = 0;        // all units' statistics bins, contiguous: zeroed by ONE launch per training forward
     size_t off_bnws = 0, bnws_bytes = 0, off_wgws = 0, wgws_bytes = 0, off_headdw = 0, off_headpart = 0, off_dyh = 0, off_dup = 0,
            off_zs = 0, off_idx = 0;
-    size_t ws_eval = 0, ws_train = 0, off_logits = 0, off_bncnt = 0;
+    size_t ws_eval = 0, ws_train = 0, off_logits = 0;
+    size_t off_bncnt = 0;                        // reserved, unused: 256 bytes that keep every later offset (and the pinned plans) where it is
     int last_n = 0;
     std::vector<char> group_first;  // optimiser groups of the fused backward (see unet_backward_range)
     std::vector<int> producer, first_consumer;   // per activation: unit that outputs it / lowest-index unit that reads it

@@ -790,7 +790,7 @@ size_t plan_workspace(vs_unet* net) {
     for (auto& u : net->units) cmax = std::max(cmax, u.cout);
     net->bnws_bytes = 4 * vs_bn_workspace(0, cmax);  // also receives the conv epilogue's per-tile statistics
     net->off_bnws = take(net->bnws_bytes);
-    net->off_bncnt = take(256);                      // grid-barrier counters of the one-launch BatchNorm backward (zeroed by vs_unet_prepare)
+    net->off_bncnt = take(256);                      // reserved, unused (zeroed by vs_unet_prepare): taking them out moves every later offset
     net->off_syncsc = take((size_t)2 * cmax * sizeof(float));
     {   // fixed-point statistics bins of every convolution + BatchNorm unit (ConvParams::stats_bins): one contiguous block
         size_t total = 0;
