@@ -869,6 +869,47 @@ int vs_components_apply(const uint8_t* labels, const int32_t* comp, const int32_
  * Two launches (initial values, sweep), no host loop; a volume of one value issues global atomics per wave, not per voxel. */
 int vs_component_moments(const uint8_t* labels, const int32_t* comp, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X, int64_t rows,
                          int64_t* table, void* stream);
+/* vs_object_moments: the same 20 figures, table and launches for ANY labelling whose ids are member voxel indices - objects[v] (n
+ * int32, 16-byte aligned) names the object of voxel v by one of the object's voxels, and row_of_root is read at that voxel.  A run is
+ * a stretch of equal id; an exposed face (16 - 18) is a face neighbour with ANOTHER ID or outside the volume, so the contact
+ * between two objects of one label value counts as surface of both.  On the comp of vs_label_components it returns the bits of
+ * vs_component_moments (components of one value are never face-adjacent).  One kernel, two instantiations. */
+int vs_object_moments(const int32_t* objects, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X, int64_t rows, int64_t* table,
+                      void* stream);
+
+/* ---- touching objects apart: distance-map watershed of one label value (csrc/separate.hip) ----
+ * Z x Y x X volumes, x fastest, n = Z * Y * X < 2^31 voxels (otherwise VS_ERR_INVALID); connectivity 6, 18 or 26 as in
+ * vs_label_components, an axis of length 1 has no neighbours.  r: n uint32, the squared distance of every voxel of one label value
+ * to the nearest voxel of another value and 0 at the voxels of the other values (vs_edt_squared with seeds = labels != value).  The
+ * key of a voxel is (r << 32) | (0xFFFFFFFF - index).  utilities/separation.py states the definitions, holds the host merge
+ * between vs_separate_pairs and vs_separate_relabel, and a host route that gives the same integers.  Exact integers: every result
+ * is the same bits on every run (the pair table once it is sorted by key).  No kernel waits on another workgroup; no host loop.
+ *
+ * vs_separate_parents: parent[v] (n int32, fully written) = the voxel with the largest key among v and its neighbours, v itself at a
+ * peak, -1 where r[v] == 0.  One launch; the stencil reads a tile with its halo from LDS.
+ * vs_separate_basins: in place, parent[v] becomes the peak at which the chain v -> parent[v] -> ... ends; -1 stays.  Two launches:
+ * chains are resolved inside 8 x 8 x 64 tiles in LDS by pointer jumping, then followed from tile to tile with write-back.
+ * vs_separate_pair_count: count[0] (one device int64, 8-byte aligned, written by the call) = the adjacent voxel pairs whose basins
+ * (both >= 0) differ.  It bounds the rows of the table below, as does B (B - 1) / 2 for B basins.
+ * vs_separate_pairs: keys[s] / saddle[s] / faces[3 s .. 3 s + 2] (slots uint64 / uint32 / 3 int32 each, slots a power of two, all
+ * initialised by the call) = an open-addressing table with one row per unordered pair of adjacent basins A < B: key = (A << 32) | B
+ * (a free slot reads 0xFFFFFFFFFFFFFFFF), saddle = the largest min(r[u], r[v]) over the adjacent u in A, v in B, faces = the
+ * face-adjacent pairs among them across z, y, x.  used (2 device int64): used[0] = the occupied slots, used[1] = 1 when an insertion
+ * found no slot within `slots` probes - the call then returns VS_ERR_INVALID and vs_last_error names the table size.  A wave
+ * aggregates equal keys before it touches the table; every probe loop ends after `slots` steps.  Four memsets and one launch; the call
+ * waits for the stream before it returns, to read `used`.
+ * vs_separate_relabel: set_of_peak (n int32, read at peaks only) names the representative peak of every peak's merged set.
+ * objects[v] = the lowest voxel index among the voxels whose basin's representative is that of v's, wherever basin[v] >= 0; every
+ * other element of objects is left alone, so several label values share one labelling.  workspace: vs_separate_workspace_bytes
+ * bytes, 4-byte aligned.  One memset and two launches. */
+int vs_separate_parents(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, int connectivity, int32_t* parent, void* stream);
+int vs_separate_basins(int32_t* parent, int64_t Z, int64_t Y, int64_t X, void* stream);
+int vs_separate_pair_count(const int32_t* basin, int64_t Z, int64_t Y, int64_t X, int connectivity, int64_t* count, void* stream);
+int vs_separate_pairs(const uint32_t* r, const int32_t* basin, int64_t Z, int64_t Y, int64_t X, int connectivity, uint64_t* keys,
+                      uint32_t* saddle, int32_t* faces, int64_t slots, int64_t* used, void* stream);
+size_t vs_separate_workspace_bytes(int64_t Z, int64_t Y, int64_t X);
+int vs_separate_relabel(const int32_t* basin, const int32_t* set_of_peak, int64_t Z, int64_t Y, int64_t X, int32_t* objects,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- surface meshes of a label volume (csrc/mesh.hip) ----
  * The naive surface net of M = the voxels of a Z x Y x X uint8 label volume (x fastest) whose value is `value`; everything outside

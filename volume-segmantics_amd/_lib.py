@@ -270,6 +270,13 @@ _SIGS = {
     "vs_component_largest": (I, [P, P, I64, P, P]),
     "vs_components_apply": (I, [P, P, P, P, P, P, I, I64, I64, P, P, P]),
     "vs_component_moments": (I, [P, P, P, I64, I64, I64, I64, P, P]),
+    "vs_object_moments": (I, [P, P, I64, I64, I64, I64, P, P]),
+    "vs_separate_parents": (I, [P, I64, I64, I64, I, P, P]),
+    "vs_separate_basins": (I, [P, I64, I64, I64, P]),
+    "vs_separate_pair_count": (I, [P, I64, I64, I64, I, P, P]),
+    "vs_separate_pairs": (I, [P, P, I64, I64, I64, I, P, P, P, I64, P, P]),
+    "vs_separate_workspace_bytes": (SZ, [I64, I64, I64]),
+    "vs_separate_relabel": (I, [P, P, I64, I64, I64, P, P, SZ, P]),
     "vs_mesh_workspace_bytes": (SZ, [I64, I64, I64]),
     "vs_mesh_count": (I, [P, I64, I64, I64, I, P, SZ, P, P]),
     "vs_mesh_emit": (I, [P, I64, I64, I64, I, I, P, SZ, P, P, P]),

@@ -31,6 +31,13 @@
 //    go straight to global atomics on addresses that are spread.
 //  A volume of one value issues at most 20 global atomics per wave (one wave per 8192 voxels), and so does the border between two
 //  big objects; random labels with every crumb measured pay one eviction per run, which is what they would pay without a cache.
+//
+// vs_object_moments: the same sweep for ANY labelling whose ids are member voxel indices (the separated objects of
+// utilities/separation.py): a run is a stretch of equal ID and an exposed face a face neighbour with another id, so two objects of
+// one value that touch count their contact as surface.  It is the second instantiation of the one kernel - the policy (ByValue /
+// ById) says what a run and a neighbour are compared by and how four elements are loaded (one 4-byte word / one 16-byte vector per
+// lane and neighbouring row); everything after the ballots is shared.  On a component labelling the two give the same bits:
+// components of one value are never face-adjacent.
 #include <limits.h>
 
 #include "common.h"
@@ -78,20 +85,46 @@ __device__ __forceinline__ void flush_slot(long long* __restrict__ table, long l
     }
 }
 
-// the four bytes labels[a .. a + 3] as one word, 0 for a byte outside the volume; one load where the address allows it
-__device__ __forceinline__ uint32_t load4(const uint8_t* __restrict__ labels, int64_t a, int64_t n, bool aligned) {
-    if (aligned && a >= 0 && a + 4 <= n) return *reinterpret_cast<const uint32_t*>(labels + a);
-    uint32_t w = 0;
+// What delimits a run and what a neighbour is compared by is the sweep's policy; the wave cache, the closed forms and the group
+// figures are shared.  A policy loads the four elements src[a .. a + 3] as one word (anything for an element outside the volume:
+// the sweep asks for the coordinate first), hands lane l of sub-step k element 64 k + l of the step - element l % 4 of the word
+// that lane 16 k + l / 4 loaded - and names the component of a run from its first voxel.
+struct ByValue {                               // vs_component_moments: runs and faces from the label VALUE, the id read once per run
+    using Elem = uint8_t;
+    using Word = uint32_t;
+    static __device__ __forceinline__ Word load(const Elem* __restrict__ labels, int64_t a, int64_t n, bool aligned) {
+        if (aligned && a >= 0 && a + 4 <= n) return *reinterpret_cast<const uint32_t*>(labels + a);
+        uint32_t w = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (a + j >= 0 && a + j < n) w |= (uint32_t)labels[a + j] << (8 * j);
-    return w;
-}
+        for (int j = 0; j < 4; ++j)
+            if (a + j >= 0 && a + j < n) w |= (uint32_t)labels[a + j] << (8 * j);
+        return w;
+    }
+    static __device__ __forceinline__ Word none() { return 0u; }
+    static __device__ __forceinline__ int pick(Word w, int k, int lane) {
+        return (int)(((uint32_t)__shfl((int)w, 16 * k + (lane >> 2), 64) >> (8 * (lane & 3))) & 0xffu);
+    }
+    static __device__ __forceinline__ int id_of(const int* __restrict__ comp, int64_t p, int) { return comp[p]; }
+};
 
-// lane l of sub-step k holds voxel 64 k + l of the step: byte l % 4 of the word that lane 16 k + l / 4 loaded
-__device__ __forceinline__ int pick(uint32_t w, int k, int lane) {
-    return (int)(((uint32_t)__shfl((int)w, 16 * k + (lane >> 2), 64) >> (8 * (lane & 3))) & 0xffu);
-}
+struct ById {                                  // vs_object_moments: runs and faces from the object ID itself, 16 bytes per lane and load
+    using Elem = int;
+    using Word = int4;
+    static __device__ __forceinline__ Word load(const Elem* __restrict__ ids, int64_t a, int64_t n, bool aligned) {
+        if (aligned && a >= 0 && a + 4 <= n) return *reinterpret_cast<const int4*>(ids + a);
+        int e[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = a + j >= 0 && a + j < n ? ids[a + j] : -1;
+        return make_int4(e[0], e[1], e[2], e[3]);
+    }
+    static __device__ __forceinline__ Word none() { return make_int4(-1, -1, -1, -1); }
+    static __device__ __forceinline__ int pick(Word w, int k, int lane) {
+        const int src = 16 * k + (lane >> 2), sel = lane & 3;
+        const int x = __shfl(w.x, src, 64), y = __shfl(w.y, src, 64), z = __shfl(w.z, src, 64), t = __shfl(w.w, src, 64);
+        return sel == 0 ? x : sel == 1 ? y : sel == 2 ? z : t;
+    }
+    static __device__ __forceinline__ int id_of(const int* __restrict__, int64_t, int own) { return own; }
+};
 
 // sum of i^2 for i = 0 .. m, m >= -1; the division comes before the last product, so no intermediate exceeds the result
 __device__ __forceinline__ long long sum_squares(long long m) {
@@ -135,7 +168,8 @@ __global__ __launch_bounds__(kThreads) void table_init_kernel(long long* __restr
     table[i] = f == 10 ? Z : f == 12 ? Y : f == 14 ? X : (f == 11 || f == 13 || f == 15) ? -1 : 0;      // an empty box: min = extent, max = -1
 }
 
-__global__ __launch_bounds__(kThreads) void moments_kernel(const uint8_t* __restrict__ labels, const int* __restrict__ comp,
+template <typename Policy>
+__global__ __launch_bounds__(kThreads) void moments_kernel(const typename Policy::Elem* __restrict__ labels, const int* __restrict__ comp,
                                                          const int* __restrict__ row_of_root, int Z, int Y, int X, int64_t n, int rows,
                                                          long long* __restrict__ table) {
     __shared__ long long cache_val[kWaves][kSlots][kFields];
@@ -148,20 +182,21 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const uint8_t* __rest
     cache_fence();
 
     const int64_t plane = (int64_t)Y * X;
-    const bool word_y = X % 4 == 0, word_z = plane % 4 == 0;           // the neighbouring rows are word aligned like the row itself
+    const bool word_y = X % 4 == 0, word_z = plane % 4 == 0;           // the neighbouring rows are aligned like the row itself
     const int64_t base = ((int64_t)blockIdx.x * kWaves + wave) * kSpanSteps * 256;
     for (int step = 0; step < kSpanSteps; ++step) {
         const int64_t sb = base + (int64_t)step * 256;
         if (sb >= n) break;                                             // uniform over the wave
         const int64_t v0 = sb + lane * 4;
-        const uint32_t wc = load4(labels, v0, n, true);
-        const uint32_t wy0 = Y > 1 ? load4(labels, v0 - X, n, word_y) : 0u, wy1 = Y > 1 ? load4(labels, v0 + X, n, word_y) : 0u;
-        const uint32_t wz0 = Z > 1 ? load4(labels, v0 - plane, n, word_z) : 0u, wz1 = Z > 1 ? load4(labels, v0 + plane, n, word_z) : 0u;
+        using Word = typename Policy::Word;
+        const Word wc = Policy::load(labels, v0, n, true);
+        const Word wy0 = Y > 1 ? Policy::load(labels, v0 - X, n, word_y) : Policy::none(), wy1 = Y > 1 ? Policy::load(labels, v0 + X, n, word_y) : Policy::none();
+        const Word wz0 = Z > 1 ? Policy::load(labels, v0 - plane, n, word_z) : Policy::none(), wz1 = Z > 1 ? Policy::load(labels, v0 + plane, n, word_z) : Policy::none();
         const int before = sb > 0 ? (int)labels[sb - 1] : -1, after = sb + 256 < n ? (int)labels[sb + 256] : -1;      // beyond the step's ends
         int c[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int value = pick(wc, k, lane);                        // every lane shuffles: a lane beyond the volume may hold a word that is read
+            const int value = Policy::pick(wc, k, lane);                        // every lane shuffles: a lane beyond the volume may hold a word that is read
             c[k] = sb + 64 * k + lane < n ? value : -1;
         }
 
@@ -182,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const uint8_t* __rest
             const bool start = valid && (lane == 0 || xs[k] == 0 || left != c[k]);
             starts_of[k] = __ballot(start);
             valids_of[k] = __ballot(valid);
-            ids[k] = start ? comp[p] : -1;
+            ids[k] = start ? Policy::id_of(comp, p, c[k]) : -1;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -207,7 +242,7 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const uint8_t* __rest
             if (lane == 0) left = edge_l;
             if (lane == 63) right = edge_r;
 
-            const int ny0 = pick(wy0, k, lane), ny1 = pick(wy1, k, lane), nz0 = pick(wz0, k, lane), nz1 = pick(wz1, k, lane);
+            const int ny0 = Policy::pick(wy0, k, lane), ny1 = Policy::pick(wy1, k, lane), nz0 = Policy::pick(wz0, k, lane), nz1 = Policy::pick(wz1, k, lane);
             const uint64_t bx0 = __ballot(valid && X > 1 && (x == 0 || left != cc)), bx1 = __ballot(valid && X > 1 && (x == X - 1 || right != cc));
             const uint64_t by0 = __ballot(valid && Y > 1 && (y == 0 || ny0 != cc)), by1 = __ballot(valid && Y > 1 && (y == Y - 1 || ny1 != cc));
             const uint64_t bz0 = __ballot(valid && Z > 1 && (z == 0 || nz0 != cc)), bz1 = __ballot(valid && Z > 1 && (z == Z - 1 || nz1 != cc));
@@ -274,6 +309,22 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const uint8_t* __rest
         if (key[slot] >= 0) flush_slot(table, val[slot], key[slot], lane);
 }
 
+// the two launches of either form: the table's initial values, then the sweep
+template <typename Policy>
+int launch_moments(const typename Policy::Elem* elems, const int32_t* comp, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X, int64_t rows,
+                   int64_t* table, double bytes_per_voxel, hipStream_t s) {
+    const int64_t n = Z * Y * X, entries = rows * kFields;
+    hipLaunchKernelGGL(table_init_kernel, dim3((unsigned)((entries + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (long long*)table, entries,
+                       (int)Z, (int)Y, (int)X);
+    VS_LAUNCH_CHECK();
+    const int64_t per_wg = (int64_t)kWaves * kSpanSteps * 256;
+    ProfScope prof(PK_POOL_MISC, 0.0, bytes_per_voxel * (double)n, s);
+    hipLaunchKernelGGL(moments_kernel<Policy>, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(kThreads), 0, s, elems, comp, row_of_root, (int)Z, (int)Y,
+                       (int)X, n, (int)rows, (long long*)table);
+    VS_LAUNCH_CHECK();
+    return VS_OK;
+}
+
 }  // namespace
 
 extern "C" int vs_component_moments(const uint8_t* labels, const int32_t* comp, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X,
@@ -287,15 +338,19 @@ extern "C" int vs_component_moments(const uint8_t* labels, const int32_t* comp, 
     VS_REQUIRE(labels && comp && row_of_root && table, "component_moments: null argument");
     VS_REQUIRE(((uintptr_t)labels | (uintptr_t)comp | (uintptr_t)row_of_root) % 4 == 0 && (uintptr_t)table % 8 == 0,
                "component_moments: labels, comp and row_of_root must be 4-byte, the table 8-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t entries = rows * kFields;
-    hipLaunchKernelGGL(table_init_kernel, dim3((unsigned)((entries + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, (long long*)table, entries,
-                       (int)Z, (int)Y, (int)X);
-    VS_LAUNCH_CHECK();
-    const int64_t per_wg = (int64_t)kWaves * kSpanSteps * 256;
-    ProfScope prof(PK_POOL_MISC, 0.0, 5.0 * (double)n, s);               // labels and their four neighbouring rows; ids and rows once per run
-    hipLaunchKernelGGL(moments_kernel, dim3((unsigned)((n + per_wg - 1) / per_wg)), dim3(kThreads), 0, s, labels, comp, row_of_root, (int)Z, (int)Y,
-                       (int)X, n, (int)rows, (long long*)table);
-    VS_LAUNCH_CHECK();
-    return VS_OK;
+    return launch_moments<ByValue>(labels, comp, row_of_root, Z, Y, X, rows, table, 5.0, (hipStream_t)stream);      // labels and their four neighbouring rows; ids and rows once per run
+}
+
+extern "C" int vs_object_moments(const int32_t* objects, const int32_t* row_of_root, int64_t Z, int64_t Y, int64_t X, int64_t rows, int64_t* table,
+                                 void* stream) {
+    VS_REQUIRE(extents_fit(Z, Y, X, 0), "object_moments: extents %lld x %lld x %lld - every extent must be at least 1 and the volume below 2^31 "
+               "voxels (object ids are int32 voxel indices)", (long long)Z, (long long)Y, (long long)X);
+    const int64_t n = Z * Y * X;
+    VS_REQUIRE(rows >= 0 && rows <= n, "object_moments: %lld rows - a volume of %lld voxels has between 0 and that many objects", (long long)rows,
+               (long long)n);
+    if (rows == 0) return VS_OK;
+    VS_REQUIRE(objects && row_of_root && table, "object_moments: null argument");
+    VS_REQUIRE((uintptr_t)objects % 16 == 0 && (uintptr_t)row_of_root % 4 == 0 && (uintptr_t)table % 8 == 0,
+               "object_moments: objects must be 16-byte, row_of_root 4-byte, the table 8-byte aligned");
+    return launch_moments<ById>(objects, nullptr, row_of_root, Z, Y, X, rows, table, 20.0, (hipStream_t)stream);     // ids and their four neighbouring rows
 }

@@ -32,7 +32,7 @@ def _clean(volume, settings, device):
 
 
 def _write_measurements(stem, m, save):
-    measurements.write_measurements(stem, m["raw"], m["table"], m["settings"])
+    measurements.write_measurements(stem, m["raw"], m["table"], m["settings"], m.get("separation"))
     if m["ids"] is not None:
         save(m["ids"], f"{stem}_object_ids.h5")
 
@@ -52,7 +52,7 @@ LABEL_STEPS = (
     LabelStep("measure", lambda s: bool(getattr(s, "measure_objects", False)),
               "there are no objects to measure (unset measure_objects or set one_hot: False)",
               lambda volume, s, device: (volume, measurements.measure_label_volume(volume, s, device=device)),
-              lambda m: "Objects of the label volume:\n" + measurements.object_table_text(m["table"]),
+              lambda m: "Objects of the label volume:\n" + measurements.object_table_text(m["table"]) + measurements.separation_text(m),
               "last_measurements", _write_measurements),
     LabelStep("mesh", lambda s: bool(getattr(s, "mesh_surfaces", False)),
               "there is no surface to mesh (unset mesh_surfaces or set one_hot: False)",
@@ -86,7 +86,10 @@ class VolSeg2DPredictionManager(BaseDataManager):
         per connected component under ``measure_connectivity``, at least ``measure_min_voxels`` voxels, the background with
         ``measure_background``, physical units from ``measure_voxel_size``): the summary is logged, ``last_measurements`` keeps the raw
         integers and the table, and ``<stem>_objects.csv`` / ``.json`` - with ``measure_save_ids`` also ``<stem>_object_ids.h5`` - are
-        written beside the label volume.
+        written beside the label volume.  With ``measure_separate: true`` as well the rows, the ids and the files describe the objects a
+        distance-map watershed takes apart (utilities/separation.py: ``measure_separate_values``, ``measure_separate_depth``,
+        ``measure_separate_max_pairs``), ``last_measurements["separation"]`` keeps the report and the contacts, and
+        ``<stem>_object_contacts.csv`` / ``.json`` list the pairs of touching objects.
         With ``mesh_surfaces: true`` the same volume is meshed (utilities/meshes.py: per value of ``mesh_values`` a closed surface net in
         ``mesh_style``, physical units from ``mesh_voxel_size``): the summary is logged, ``last_meshes`` keeps the arrays and the figures,
         and ``<stem>_mesh_<value>.ply`` / ``.stl`` (``mesh_format``, ``mesh_triangulate``) and ``<stem>_meshes.json`` are written beside the

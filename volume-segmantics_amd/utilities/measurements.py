@@ -63,19 +63,21 @@ def _select_host(sizes, values, min_voxels: int, background: int, include_backgr
 
 
 def _exposed_host(vol: np.ndarray, axis: int) -> np.ndarray:
-    """per voxel the exposed faces across `axis` (0, 1 or 2): shifted comparisons on a padded copy"""
+    """per voxel the exposed faces across `axis` (0, 1 or 2): shifted comparisons on a padded copy.  `vol` holds label values, or - the
+    id-based form - the object ids of a labelling: a face neighbour with another id is then exposed, whatever its value"""
     if vol.shape[axis] == 1:
         return np.zeros(vol.shape, dtype=np.uint8)
     pad = [(0, 0)] * 3
     pad[axis] = (1, 1)
-    padded = np.pad(vol.astype(np.int16), pad, constant_values=-1)
+    padded = np.pad(vol.astype(np.int16 if vol.dtype == np.uint8 else np.int64), pad, constant_values=-1)
     lo, hi = [slice(None)] * 3, [slice(None)] * 3
     lo[axis], hi[axis] = slice(0, -2), slice(2, None)
     return (padded[tuple(lo)] != vol).astype(np.uint8) + (padded[tuple(hi)] != vol).astype(np.uint8)
 
 
-def _table_host(vol: np.ndarray, comp: np.ndarray, row_of_root: np.ndarray, rows: int) -> np.ndarray:
-    """the (rows, 20) table by sorting the measured voxels by row and summing each stretch in int64"""
+def _table_host(vol: np.ndarray, comp: np.ndarray, row_of_root: np.ndarray, rows: int, by_id: bool = False) -> np.ndarray:
+    """the (rows, 20) table by sorting the measured voxels by row and summing each stretch in int64; `by_id`: exposed faces from the
+    ids of `comp` (separated objects) instead of the values of `vol`"""
     table = np.zeros((rows, len(FIELDS)), dtype=np.int64)
     if rows == 0:
         return table
@@ -91,13 +93,20 @@ def _table_host(vol: np.ndarray, comp: np.ndarray, row_of_root: np.ndarray, rows
     for axis, (letter, coord) in enumerate((("z", z), ("y", y), ("x", x))):
         table[:, F["min_" + letter]] = np.minimum.reduceat(coord, starts)
         table[:, F["max_" + letter]] = np.maximum.reduceat(coord, starts)
-        table[:, F["faces_" + letter]] = np.add.reduceat(_exposed_host(vol, axis).reshape(-1)[order].astype(np.int64), starts)
+        table[:, F["faces_" + letter]] = np.add.reduceat(_exposed_host(comp.reshape(vol.shape) if by_id else vol, axis).reshape(-1)[order].astype(np.int64), starts)
     table[:, F["touches_border"]] = np.maximum.reduceat(lv.touch_mask(vol.shape).reshape(-1)[order].astype(np.int64), starts)
     return table
 
 
-def _measure_host(vol: np.ndarray, connectivity: int, min_voxels: int, background: int, include_background: bool, want_ids: bool):
-    comp = co.label_components(vol, connectivity, device="cpu")
+def _measure_host(vol: np.ndarray, connectivity: int, min_voxels: int, background: int, include_background: bool, want_ids: bool,
+                  separate: dict | None = None):
+    separation = None
+    if separate is None:
+        comp = co.label_components(vol, connectivity, device="cpu")
+    else:
+        from . import separation as sp
+        comp, report, contacts = sp.separate_prepared(vol, vol.shape, None, separate["values"], connectivity, separate["depth"], separate["max_pairs"])
+        separation = dict(report=report, contacts=contacts)
     flat_c = comp.reshape(-1)
     size = np.bincount(flat_c, minlength=flat_c.size)
     roots = np.flatnonzero(size).astype(np.int64)
@@ -107,9 +116,9 @@ def _measure_host(vol: np.ndarray, connectivity: int, min_voxels: int, backgroun
     roots, values = roots[keep][order], values[keep][order]
     row_of_root = np.full(flat_c.size, -1, dtype=np.int32)
     row_of_root[roots] = np.arange(len(roots), dtype=np.int32)
-    table = _table_host(vol, comp, row_of_root, len(roots))
+    table = _table_host(vol, comp, row_of_root, len(roots), by_id=separate is not None)
     ids = (row_of_root[flat_c] + 1).reshape(vol.shape) if want_ids else None
-    return dict(table=table, roots=roots, values=values, not_listed_objects=objects, not_listed_voxels=voxels), ids
+    return dict(table=table, roots=roots, values=values, not_listed_objects=objects, not_listed_voxels=voxels), ids, separation
 
 
 # ---- device route ----------------------------------------------------------------------------------------------------------------
@@ -124,11 +133,28 @@ def _moments_device(labels_dev, comp, row_of_root, zyx, rows: int):
     return table
 
 
-def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, background: int, include_background: bool, want_ids: bool):
+def _object_moments_device(objects, row_of_root, zyx, rows: int):
+    """vs_object_moments: the (rows, 20) int64 table of a labelling by member voxel ids, on the device"""
+    import torch
+    from .. import _lib
+    table = torch.empty((rows, len(FIELDS)), dtype=torch.int64, device=objects.device)
+    with torch.cuda.device(objects.device):
+        _lib.check(_lib.lib.vs_object_moments(_lib.ptr(objects), _lib.ptr(row_of_root), *zyx, rows, _lib.ptr(table), _lib.stream_ptr()))
+    return table
+
+
+def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, background: int, include_background: bool, want_ids: bool,
+                    separate: dict | None = None):
     import torch
     n = v.numel()
     lv.require_memory(device, 4 * n + (4 * n if want_ids else 0), f"the row of every root of a {tuple(zyx)} volume")
-    comp = co.label_device(v, zyx, connectivity)
+    separation = None
+    if separate is None:
+        comp = co.label_device(v, zyx, connectivity)
+    else:
+        from . import separation as sp
+        comp, report, contacts = sp.separate_prepared(v, zyx, device, separate["values"], connectivity, separate["depth"], separate["max_pairs"])
+        separation = dict(report=report, contacts=contacts)
     size, _ = co.sizes_device(comp, zyx)
     roots = torch.nonzero(size).reshape(-1)                           # ascending
     sizes, values = size[roots].to(torch.int64), v[roots].to(torch.int64)
@@ -144,35 +170,41 @@ def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, backgrou
     lv.require_memory(device, 8 * len(FIELDS) * rows, f"the table of {rows} components")
     row_of_root = torch.full((n,), -1, dtype=torch.int32, device=device)
     row_of_root[roots] = torch.arange(rows, dtype=torch.int32, device=device)
-    table = _moments_device(v, comp, row_of_root, zyx, rows)
+    table = _moments_device(v, comp, row_of_root, zyx, rows) if separate is None else _object_moments_device(comp, row_of_root, zyx, rows)
     ids = (row_of_root[comp.to(torch.int64)] + 1).cpu().numpy().reshape(zyx) if want_ids else None
     host = lambda t: t.cpu().numpy().astype(np.int64)                 # noqa: E731
-    return dict(table=host(table), roots=host(roots), values=host(values), not_listed_objects=host(objects), not_listed_voxels=host(voxels)), ids
+    return dict(table=host(table), roots=host(roots), values=host(values), not_listed_objects=host(objects), not_listed_voxels=host(voxels)), ids, separation
 
 
 # ---- public: the integers --------------------------------------------------------------------------------------------------------
-def _measure(vol, connectivity, min_voxels, background, include_background, device, want_ids):
+def _measure(vol, connectivity, min_voxels, background, include_background, device, want_ids, separate=None):
+    """``separate`` (None, or the ``values``, ``depth`` and ``max_pairs`` of ``separation.separation_settings``): measure the objects of
+    ``separation.separate_objects`` in place of the components; the third result is then its report and contacts, else None"""
     _check_sums_fit(vol.shape)
     min_voxels, background = _arguments(min_voxels, background)
     shape, zyx, device, v = co.prepare(vol, connectivity, device)
     if device is None:
-        raw, ids = _measure_host(v, int(connectivity), min_voxels, background, bool(include_background), want_ids)
+        raw, ids, separation = _measure_host(v, int(connectivity), min_voxels, background, bool(include_background), want_ids, separate)
     else:
-        raw, ids = _measure_device(v, zyx, device, int(connectivity), min_voxels, background, bool(include_background), want_ids)
+        raw, ids, separation = _measure_device(v, zyx, device, int(connectivity), min_voxels, background, bool(include_background), want_ids, separate)
     raw["shape"] = np.array(zyx, dtype=np.int64)
-    return raw, (None if ids is None else ids.astype(np.int32, copy=False).reshape(shape))
+    return raw, (None if ids is None else ids.astype(np.int32, copy=False).reshape(shape)), separation
 
 
-def measure_components(vol, connectivity: int = 6, min_voxels: int = 1, background: int = 0, include_background: bool = False, device=None) -> dict:
+def measure_components(vol, connectivity: int = 6, min_voxels: int = 1, background: int = 0, include_background: bool = False, device=None,
+                       separate: dict | None = None) -> dict:
     """The raw integers, as int64 arrays: ``table`` (rows, 20) in the order of ``FIELDS``, ``roots`` and ``values`` (rows,),
     ``not_listed_objects`` / ``not_listed_voxels`` (256, per label value: the components that got no row) and ``shape`` (Z, Y, X).
-    Row order: value ascending, then root ascending; object id = row + 1."""
-    return _measure(vol, connectivity, min_voxels, background, include_background, device, False)[0]
+    Row order: value ascending, then root ascending; object id = row + 1.  ``separate`` (a dict with ``values``, ``depth`` and
+    ``max_pairs``, see ``utilities/separation.py``): one row per separated OBJECT - its root is the object's lowest voxel, and a face
+    between two objects of one value counts as exposed."""
+    return _measure(vol, connectivity, min_voxels, background, include_background, device, False, separate)[0]
 
 
-def object_ids(vol, connectivity: int = 6, min_voxels: int = 1, background: int = 0, include_background: bool = False, device=None) -> np.ndarray:
+def object_ids(vol, connectivity: int = 6, min_voxels: int = 1, background: int = 0, include_background: bool = False, device=None,
+               separate: dict | None = None) -> np.ndarray:
     """int32 array of ``vol.shape``: the object id (row of ``measure_components`` + 1) of every voxel, 0 where it is not measured."""
-    return _measure(vol, connectivity, min_voxels, background, include_background, device, True)[1]
+    return _measure(vol, connectivity, min_voxels, background, include_background, device, True, separate)[1]
 
 
 # ---- public: the derived figures ---------------------------------------------------------------------------------------------------
@@ -275,10 +307,18 @@ def measurement_settings(settings) -> dict:
 
 def measure_label_volume(vol, settings, device=None) -> dict:
     """``measure_components`` and ``object_table`` with the settings keys: ``{"settings", "raw", "table", "ids"}`` (``ids``: the int32
-    object-id volume with ``measure_save_ids``, else None).  Measures whether or not ``measure_objects`` is set: calling is the request."""
+    object-id volume with ``measure_save_ids``, else None).  Measures whether or not ``measure_objects`` is set: calling is the request.
+    With ``measure_separate: true`` the rows and the ids are those of the separated objects (``utilities/separation.py``) and the
+    result has a further key ``"separation"``: its ``settings``, the per-value ``report`` and the ``contacts`` table."""
     m = measurement_settings(settings)
-    raw, ids = _measure(vol, m["connectivity"], m["min_voxels"], 0, m["include_background"], device, m["save_ids"])
-    return {"settings": m, "raw": raw, "table": object_table(raw, m["voxel_size"]), "ids": ids}
+    from . import separation as sp
+    s = sp.separation_settings(settings)
+    if not s["active"]:
+        raw, ids, _ = _measure(vol, m["connectivity"], m["min_voxels"], 0, m["include_background"], device, m["save_ids"])
+        return {"settings": m, "raw": raw, "table": object_table(raw, m["voxel_size"]), "ids": ids}
+    raw, ids, separation = _measure(vol, m["connectivity"], m["min_voxels"], 0, m["include_background"], device, m["save_ids"], s)
+    separation = dict(settings=s, report=separation["report"], contacts=sp.contacts_table(separation["contacts"], raw["roots"], m["voxel_size"]))
+    return {"settings": m, "raw": raw, "table": object_table(raw, m["voxel_size"]), "ids": ids, "separation": separation}
 
 
 def object_table_text(table: dict, largest: int = 10) -> str:
@@ -299,10 +339,23 @@ def object_table_text(table: dict, largest: int = 10) -> str:
     return "\n".join(lines)
 
 
-def write_measurements(stem, raw: dict, table: dict, settings: dict | None = None) -> list[Path]:
+def separation_text(m: dict) -> str:
+    """what the log adds where ``measure_label_volume`` separated touching objects: the per-value report and the number of contacts;
+    empty otherwise"""
+    if m.get("separation") is None:
+        return ""
+    from . import separation as sp
+    s = m["separation"]
+    return (f"\nTouching objects taken apart at depth {s['settings']['depth']} ({len(s['contacts']['id_a'])} contacts):\n"
+            + sp.separation_text(s["report"]))
+
+
+def write_measurements(stem, raw: dict, table: dict, settings: dict | None = None, separation: dict | None = None) -> list[Path]:
     """``<stem>_objects.csv`` (one row per object, the columns of ``COLUMNS``) and ``<stem>_objects.json``: the settings, the summary
     and per object its id, value, root, the raw integers (``fields`` names them) and the derived figures - the integers make the
-    file reproducible to the bit; NaN is written as null."""
+    file reproducible to the bit; NaN is written as null.  ``separation`` (the key of that name of ``measure_label_volume``): the rows are
+    separated objects - the JSON gains a ``separation`` section (settings and per-value report) and ``<stem>_object_contacts.csv`` /
+    ``.json`` are written as well."""
     stem = str(stem)
     written = [Path(stem + "_objects.csv"), Path(stem + "_objects.json")]
     o = table["objects"]
@@ -321,8 +374,13 @@ def write_measurements(stem, raw: dict, table: dict, settings: dict | None = Non
            "summary": {value: {k: (lv.json_number(x) if isinstance(x, float) else x) for k, x in row.items()} for value, row in table["summary"].items()},
            "objects": [{"id": int(o["id"][i]), "value": int(o["value"][i]), "root": int(o["root"][i]), "raw": [int(x) for x in raw_table[i]],
                         "derived": {name: lv.json_number(o[name][i]) for name in COLUMNS if name not in _INT_COLUMNS}} for i in range(rows)]}
+    if separation is not None:
+        from . import separation as sp
+        doc["separation"] = {"settings": sp.json_settings(separation["settings"]), "report": separation["report"]}
     with open(written[1], "w") as f:
         json.dump(doc, f, indent=1)
+    if separation is not None:
+        written += sp.write_contacts(stem, separation["contacts"], separation["settings"], separation["report"])
     return written
 
 
