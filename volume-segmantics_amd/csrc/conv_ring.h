@@ -99,6 +99,11 @@ __global__ __launch_bounds__(NW * 64, WPS) void conv_ring_kernel(ConvParams p, G
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane >> 4, lr = lane & 15;
+    // every kernel argument the prologue reads, in ONE batch of scalar loads (see conv_igemm_kernel): loaded where first used they
+    // are three dependent round trips in front of the first DMA piece
+    asm volatile("" ::"s"(p.src0), "s"(p.src1), "s"(p.w), "s"(p.C0), "s"(p.C1), "s"(p.up0), "s"(p.N), "s"(p.Hin), "s"(p.Win), "s"(p.Cout),
+                 "s"(g.tiles_h), "s"(g.tiles_w), "s"(g.groups), "s"(g.xcs), "s"(g.xgn), "s"(g.ctl), "s"(g.ct_magic), "s"(g.ti_magic),
+                 "s"(g.tw_magic), "s"(g.probe));
     unsigned long long tprobe[5];
     if (g.probe) tprobe[0] = wall_clock64();
 
@@ -294,9 +299,14 @@ __global__ __launch_bounds__(NW * 64, WPS) void conv_ring_kernel(ConvParams p, G
     };
     read_frags(smem, 0, wf[0], xf[0]);
     read_frags(smem, 1, wf[1], xf[1]);
+    // The epilogue's parameters are read again from the kernel-argument segment (p is the first argument): held in scalar
+    // registers across the main loop they would crowd out the descriptors the DMA statements need there.  The last chunk issues
+    // no piece, so the descriptors are dead from its top on: the reload goes there and returns under the chunk's MFMAs.
+    ConvParams pe;
     // one chunk: 9 taps.  MORE: another chunk follows (its stage is read from tap 7 on)
     auto chunk_body = [&](int c, auto more_) {
         constexpr bool more = decltype(more_)::value != 0;
+        if constexpr (!more) pe = reload_first_kernarg<ConvParams>();
         const int s = c & 1;
         const char* cur = smem + s * STAGE_B;
         const char* nxt = smem + (s ^ 1) * STAGE_B;
@@ -341,9 +351,6 @@ __global__ __launch_bounds__(NW * 64, WPS) void conv_ring_kernel(ConvParams p, G
     chunk_body(nch - 1, IC<0>{});
 
     if (g.probe) tprobe[3] = wall_clock64();
-    // The epilogue's parameters are read again from the kernel-argument segment (p is the first argument): held in scalar
-    // registers across the main loop they would crowd out the descriptors the DMA statements need there.
-    const ConvParams pe = reload_first_kernarg<ConvParams>();
     if constexpr (IMGS > 1) {   // the IMGS images of the tile as one tall image: same memory, same epilogue
         ConvParams q = pe;
         q.Hout = nimg * pe.Hout;

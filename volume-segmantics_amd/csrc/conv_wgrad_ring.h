@@ -74,6 +74,10 @@ __global__ __launch_bounds__(256, WPS) void conv_wgrad_ring_kernel(WgradParams p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane >> 4, lr = lane & 15;
     const int wc = wave & 1, wt = wave >> 1;
+    // every kernel argument the prologue reads, in ONE batch of scalar loads (see conv_igemm_kernel)
+    asm volatile("" ::"s"(p.src0), "s"(p.src1), "s"(p.dy), "s"(p.C0), "s"(p.C1), "s"(p.up0), "s"(p.N), "s"(p.Hin), "s"(p.Win), "s"(p.Hout),
+                 "s"(p.Wout), "s"(p.Cout), "s"(g.tiles_h), "s"(g.tiles_w), "s"(g.total_tiles), "s"(g.cchunks), "s"(g.nsplit), "s"(g.xmode),
+                 "s"(g.npairs), "s"(g.ppx), "s"(g.tw_magic), "s"(g.th_magic), "s"(g.probe));
     unsigned long long tprobe[5];
     if (g.probe) tprobe[0] = wall_clock64();
 
