@@ -110,6 +110,76 @@ def test_conv_direct_kernel(code, force_direct_kernel):
         _conv_case(code, 1, 48, 32, 24, 16, 3, 1, 1, seed=15)                  # channel tail inside the chunk
 
 
+@pytest.mark.parametrize("code", CODES)
+def test_conv_direct_kernel_statistics_rows_and_bins(code, force_direct_kernel):
+    """The strip kernel's statistics epilogue (conv_direct_kernel MODE 0 of csrc/conv_strip.h: one stats_partial row per wave, or
+    stats_bins) at a shape where every edge is ragged: N = 2, 21 x 37, 16 -> 12 channels under 6-row strips - 4 row chunks (the last
+    with 3 rows) x 3 column strips (the last with 5 columns) per image, 24 waves, lanes of quad 3 without a channel.
+    fp32: the stored output is the accumulator itself, so row gw = (n * 4 + hc) * 3 + ws must hold the sum / sum of squares of the
+    stored output over that wave's own pixels.  A lane chains at most 6 adds (its rows), then 4 shuffle levels: gamma_10 sum |v|; the
+    squares carry one more rounding each: gamma_11 sum v^2.  No other slack; this pins the row order too.
+    bf16: the totals over the rows against the float64 convolution r of the same inputs.  Per pixel the accumulator is within e (the
+    accumulation bound of tests/conv_cases.py) of r, so the sum is within sum e + gamma_10 sum (|r| + e) and the sum of squares
+    within sum (2 |r| e + e^2) + gamma_11 sum (|r| + e)^2.
+    Both: the same launch into 16 bins gives totals within 24 * 2^-25 / 24 * 2^-17 of the rows' totals (each of the 24 atomic adds
+    rounds to a unit of the fixed-point scale: batchnorm_cases.ring_nonzero_mean_figures); every row and bin is finite (rows start as
+    NaN)."""
+    import ctypes as C
+    L = lib()
+    n, h, w, cin, cout, RH, nb = 2, 21, 37, 16, 12, 6, 16
+    g = torch.Generator().manual_seed(211 + code)
+    x = rounded(torch.randn(n, cin, h, w, generator=g), code)
+    wt = rounded(torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5, code)
+    d = conv_desc(L, code, n, h, w, cin, cout, 3, 1, 1)
+    xd, wd = to_nhwc(x, code), w_krsc(wt, code)
+    chunks, strips = -(-h // RH), -(-w // 16)
+    rows = n * chunks * strips
+
+    def run(bins):
+        t = L.ConvTrain()
+        if bins:
+            acc = torch.zeros((nb, 2, cout), dtype=torch.int64, device=DEV)
+            t.stats_bins, t.stats_nb = acc.data_ptr(), nb
+        else:
+            acc = torch.full((rows, 2, cout), float("nan"), device=DEV)
+            t.stats_partial = acc.data_ptr()
+        assert L.lib.vs_conv2d_train_variant(d, t) == 16294 and L.lib.vs_conv2d_stat_rows(d, t) == 24 == rows
+        y = torch.full((n, h, w, cout), float("nan"), device=DEV, dtype=tdtype(code))
+        L.check(L.lib.vs_conv2d_train(d, L.ptr(xd), None, L.ptr(wd), None, L.ptr(y), None, C.byref(t), None))
+        sync()
+        return from_nhwc(y).double(), acc.cpu()
+
+    y, part = run(False)
+    assert torch.isfinite(y).all() and torch.isfinite(part).all()
+    part = part.double()
+    if code == 0:
+        for i in range(n):
+            for hc in range(chunks):
+                for ws in range(strips):
+                    v = y[i, :, hc * RH:min(h, hc * RH + RH), ws * 16:min(w, ws * 16 + 16)]
+                    row = part[(i * chunks + hc) * strips + ws]
+                    f1 = CC.worst((row[0] - v.sum((1, 2))).abs(), CC.gamma(10) * v.abs().sum((1, 2)))
+                    f2 = CC.worst((row[1] - (v * v).sum((1, 2))).abs(), CC.gamma(11) * (v * v).sum((1, 2)))
+                    print(f"stats row ({i}, {hc}, {ws}): sum {f1:.3g}, sum of squares {f2:.3g} of the bound")
+                    assert f1 <= 1.0 and f2 <= 1.0, (i, hc, ws, f1, f2)
+    else:
+        r = F.conv2d(x.double(), wt.double(), padding=1)
+        e = CC.gamma(2 * cin * 9) * F.conv2d(x.double().abs(), wt.double().abs(), padding=1)
+        m = r.abs() + e
+        f1 = CC.worst((part[:, 0].sum(0) - r.sum((0, 2, 3))).abs(), e.sum((0, 2, 3)) + CC.gamma(10) * m.sum((0, 2, 3)))
+        f2 = CC.worst((part[:, 1].sum(0) - (r * r).sum((0, 2, 3))).abs(),
+                      (2 * r.abs() * e + e * e).sum((0, 2, 3)) + CC.gamma(11) * (m * m).sum((0, 2, 3)))
+        print(f"stats totals {CC.DT[code]}: sum {f1:.3g}, sum of squares {f2:.3g} of the bound")
+        assert f1 <= 1.0 and f2 <= 1.0, (f1, f2)
+    _, bins = run(True)
+    tot = bins.sum(0).double()
+    assert torch.isfinite(tot).all()
+    b1 = CC.worst((tot[0] / L.lib.vs_stat_scale(0) - part[:, 0].sum(0)).abs(), torch.full((cout,), rows * 2.0 ** -25, dtype=torch.float64))
+    b2 = CC.worst((tot[1] / L.lib.vs_stat_scale(1) - part[:, 1].sum(0)).abs(), torch.full((cout,), rows * 2.0 ** -17, dtype=torch.float64))
+    print(f"bins against rows {CC.DT[code]}: sum {b1:.3g}, sum of squares {b2:.3g} of the bound")
+    assert b1 <= 1.0 and b2 <= 1.0, (b1, b2)
+
+
 @pytest.mark.parametrize("code", [1, 2])
 @pytest.mark.parametrize("case", [(2, 64, 96, 32, 1, 16, 16, 1), (3, 40, 44, 16, 0, 16, 16, 1), (1, 34, 30, 32, 1, 16, 12, 2), (2, 32, 32, 24, 0, 8, 16, 0),
                                   (1, 70, 16, 32, 1, 16, 16, 1)])

@@ -97,7 +97,9 @@ extern "C" int vs_conv2d_train(const vs_conv_desc* d, const void* src0, const vo
     const ConvPlan plan = conv_plan(d->dtype, p);
     if (p.pool0) VS_REQUIRE(plan.can_pool, "conv_train: no pooled epilogue for this geometry");
     if (p.nl_bins) VS_REQUIRE(conv_igemm_nl_ok(d->dtype, p), "conv_train: no normalise-on-load form for this layer");
-    if (p.stats_bins) VS_REQUIRE(d->dtype == VS_BF16, "conv_train: this layer's kernel has no statistics bins");   // (every bf16 kernel has them)
+    if (p.stats_bins)      // (every bf16 kernel has them, and so has the strip kernel in fp32, the other training precision: its statistics
+                           // epilogue is one piece of code; fp16 is the inference precision and has no training epilogues - launch_conv_igemm)
+        VS_REQUIRE(d->dtype == VS_BF16 || (d->dtype == VS_F32 && plan.family == CONV_DIRECT), "conv_train: this layer's kernel has no statistics bins");
     return launch_conv_igemm(d->dtype, p, (hipStream_t)stream, &plan);
 }
 

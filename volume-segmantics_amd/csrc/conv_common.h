@@ -1,4 +1,6 @@
-// Pieces shared by the convolution kernels of conv_igemm.hip (tile kernel, direct kernel, head kernel).
+// Pieces shared by the convolution kernel families: the chunk constants and mma16 (tile kernel of conv_igemm.hip, conv_ring.h,
+// conv_stream.h, the strip kernels of conv_strip.h), and conv_epilogue, the epilogue of the tile and ring kernels (the strip
+// kernels have their own).
 #pragma once
 #include <type_traits>
 
