@@ -663,6 +663,31 @@ size_t vs_mean_iou_masked_workspace(int n, int classes);
 int vs_mean_iou_masked(const float* input, const void* targets, int target_is_f32, const uint8_t* valid, int from_logits, int n,
                        int classes, int64_t hw, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Per-class loss weights (the settings key `loss_class_weights`): the calls above with class_weights = K positive floats on the
+ * device, used as given (the caller rescales them; the trainer makes them sum to K).  valid may be NULL: one entry point serves the
+ * masked and the unmasked case.
+ *   Dice:            1 - (1/K) sum_c w_c 2 I_c / max(D_c, eps); the stats in the workspace stay the unweighted {I_c, D_c}
+ *   kind 1, 2:       the BCE term is sum_c w_c sum_pix bce / (M K) (nn.BCEWithLogitsLoss(weight = w.view(1, K, 1, 1))); kind 1 adds
+ *                    beta times the weighted Dice on sigmoid(x)
+ *   kind 3:          sum_pix w_t l / sum_pix w_t (nn.CrossEntropyLoss(weight = w)); loss and gradient are 0 when sum w_t = 0
+ *   kind 4:          refused (VS_ERR_INVALID): the generalised Dice has its own inverse-volume weights
+ * A null class_weights and a workspace below vs_dice_workspace / vs_seg_loss_weighted_workspace are VS_ERR_INVALID as well; nothing
+ * is launched then.  No launch and no sweep is added to the unweighted calls; with every weight exactly 1.0 the results equal those
+ * of the unweighted (valid NULL) or _masked calls bit for bit. */
+int vs_dice_loss_fwd_weighted(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                              const float* class_weights, int n, int classes, int64_t hw, float eps, float* loss, float* workspace,
+                              size_t workspace_bytes, void* stream);
+int vs_dice_loss_bwd_weighted(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                              const float* class_weights, const float* grad_out, int n, int classes, int64_t hw, float eps,
+                              const float* workspace, float* dlogits, void* stream);
+size_t vs_seg_loss_weighted_workspace(int classes);
+int vs_seg_loss_fwd_weighted(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                             const float* class_weights, int n, int classes, int64_t hw, float alpha, float beta, float eps, float* loss,
+                             float* workspace, size_t workspace_bytes, void* stream);
+int vs_seg_loss_bwd_weighted(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                             const float* class_weights, const float* grad_out, int n, int classes, int64_t hw, const float* workspace,
+                             float* dlogits, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training augmentations on the device (get_train_augs, data/augmentations.py:68-101; applied per sample by the reference's
  * DataLoader workers, data/datasets.py:42-60)

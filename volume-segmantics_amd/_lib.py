@@ -253,6 +253,11 @@ _SIGS = {
     "vs_seg_loss_bwd_masked": (I, [I, P, P, I, P, P, I, I, I64, P, P, P]),
     "vs_mean_iou_masked_workspace": (SZ, [I, I]),
     "vs_mean_iou_masked": (I, [P, P, I, P, I, I, I, I64, P, P, SZ, P]),
+    "vs_dice_loss_fwd_weighted": (I, [P, P, I, P, P, I, I, I64, F, P, P, SZ, P]),
+    "vs_dice_loss_bwd_weighted": (I, [P, P, I, P, P, P, I, I, I64, F, P, P, P]),
+    "vs_seg_loss_weighted_workspace": (SZ, [I]),
+    "vs_seg_loss_fwd_weighted": (I, [I, P, P, I, P, P, I, I, I64, F, F, F, P, P, SZ, P]),
+    "vs_seg_loss_bwd_weighted": (I, [I, P, P, I, P, P, P, I, I, I64, P, P, P]),
     "vs_slices_gather": (I, [P, C.POINTER(DirMap), I, I, P, P]),
     "vs_slices_gather_typed": (I, [I, P, C.POINTER(DirMap), I, I, P, P]),
     "vs_logits_to_volume": (I, [P, I, C.POINTER(DirMap), I, I, I, I, P, P, P, P, I64, P]),

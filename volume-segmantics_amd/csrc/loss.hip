@@ -98,9 +98,13 @@ __global__ __launch_bounds__(256) void dice_partial4_kernel(const float* __restr
     }
 }
 
+// WEIGHTED (every kernel of this file that carries the flag): cw holds K positive class weights, used as given.  The sums and stats
+// stay unweighted; a class term of the loss and the gradient of its plane are multiplied by w_c.  A weight of exactly 1.0 leaves
+// every product as it was, so all-ones weights return the bits of the instantiation without the flag, which is the code as before.
 // one wave per class; stats[c] = {I_c, D_c}; loss written by class 0's wave after all classes are known -> single block
-__global__ __launch_bounds__(64) void dice_finalize_kernel(const float* __restrict__ partial, int nblocks, int k, float eps,
-                                                         float* __restrict__ stats, float* __restrict__ loss) {
+template <bool WEIGHTED>
+__global__ __launch_bounds__(64) void dice_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ cw, int nblocks,
+                                                         int k, float eps, float* __restrict__ stats, float* __restrict__ loss) {
     const int lane = threadIdx.x;
     double acc = 0.0;
     for (int c = 0; c < k; ++c) {
@@ -113,18 +117,20 @@ __global__ __launch_bounds__(64) void dice_finalize_kernel(const float* __restri
         for (int o = 32; o > 0; o >>= 1) { si += __shfl_xor(si, o, 64); sx += __shfl_xor(sx, o, 64); st += __shfl_xor(st, o, 64); }
         const double d = sx + st;
         if (lane == 0) { stats[2 * c] = (float)si; stats[2 * c + 1] = (float)d; }
-        acc += 2.0 * si / (d > (double)eps ? d : (double)eps);
+        const double term = 2.0 * si / (d > (double)eps ? d : (double)eps);
+        if constexpr (WEIGHTED) acc += (double)cw[c] * term;
+        else acc += term;
     }
     if (lane == 0) *loss = (float)(1.0 - acc / k);
 }
 
-template <typename TT, bool MASKED>
+template <typename TT, bool MASKED, bool WEIGHTED>
 __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict__ x, const TT* __restrict__ t,
-                                                      const uint8_t* __restrict__ valid, const float* __restrict__ stats,
-                                                      const float* __restrict__ gout, float eps, int n, int k, int64_t hw,
-                                                      float* __restrict__ dx) {
+                                                      const uint8_t* __restrict__ valid, const float* __restrict__ cw,
+                                                      const float* __restrict__ stats, const float* __restrict__ gout, float eps, int n,
+                                                      int k, int64_t hw, float* __restrict__ dx) {
     const int64_t total = (int64_t)n * k * hw;
-    const float g = (gout ? *gout : 1.f) * (-2.f / (float)k);
+    const float g1 = (gout ? *gout : 1.f) * (-2.f / (float)k);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t plane = i / hw;
         const int c = (int)(plane % k);
@@ -132,6 +138,7 @@ __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict_
             if (!valid[(size_t)(plane / k) * hw + (i - plane * hw)]) { dx[i] = 0.f; continue; }
         }
         const float I = stats[2 * c], D = stats[2 * c + 1];
+        const float g = WEIGHTED ? g1 * cw[c] : g1;
         const float xv = x[i], tv = tval(t, i);
         dx[i] = D > eps ? g * (tv * D - 2.f * xv * I) / (D * D) : g * tv / eps;
     }
@@ -139,14 +146,14 @@ __global__ __launch_bounds__(256) void dice_grad_kernel(const float* __restrict_
 
 
 // 16 bytes per lane, two vectors in flight (hw % 4 == 0: a vector never straddles two class planes)
-template <typename TT, bool MASKED>
+template <typename TT, bool MASKED, bool WEIGHTED>
 __global__ __launch_bounds__(256) void dice_grad4_kernel(const float* __restrict__ x, const TT* __restrict__ t,
-                                                       const uint8_t* __restrict__ valid, const float* __restrict__ stats,
-                                                       const float* __restrict__ gout, float eps, int n, int k, int64_t hw,
-                                                       float* __restrict__ dx) {
+                                                       const uint8_t* __restrict__ valid, const float* __restrict__ cw,
+                                                       const float* __restrict__ stats, const float* __restrict__ gout, float eps, int n,
+                                                       int k, int64_t hw, float* __restrict__ dx) {
     typedef typename TV4<TT>::type TQ;
     const int64_t nv = hw >> 2, total = (int64_t)n * k * nv, stride = (int64_t)gridDim.x * 256;
-    const float g = (gout ? *gout : 1.f) * (-2.f / (float)k);
+    const float g1 = (gout ? *gout : 1.f) * (-2.f / (float)k);
     for (int64_t v0 = (int64_t)blockIdx.x * 256 + threadIdx.x; v0 < total; v0 += 2 * stride) {
         float4 xv[2], tv[2];
         uchar4 mv[2];
@@ -169,6 +176,7 @@ __global__ __launch_bounds__(256) void dice_grad4_kernel(const float* __restrict
             const int64_t v = v0 + u * stride;
             const int c = (int)((v / nv) % k);
             const float I = stats[2 * c], D = stats[2 * c + 1];
+            const float g = WEIGHTED ? g1 * cw[c] : g1;       // (the class is uniform over a vector)
             float4 o;
             if (D > eps) {
                 const float dd = D * D;
@@ -324,9 +332,9 @@ extern "C" size_t vs_dice_workspace(int classes) { return ((size_t)kBlocks * cla
 // null and never read), MASKED = true is the same choice of kernels with the mask's alignment added to the 16-byte condition.
 namespace {
 
-template <bool MASKED>
+template <bool MASKED, bool WEIGHTED = false>
 int dice_fwd_launch(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n, int classes, int64_t hw,
-                    float eps, float* loss, float* workspace, hipStream_t s) {
+                    float eps, float* loss, float* workspace, hipStream_t s, const float* cw = nullptr) {
     float* stats = workspace + (size_t)kBlocks * classes * 3;
     const bool vec4 = (hw & 3) == 0 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)targets & (target_is_f32 ? 15 : 3)) == 0 &&
                       (!MASKED || ((uintptr_t)valid & 3) == 0);
@@ -339,14 +347,14 @@ int dice_fwd_launch(const float* logits, const void* targets, int target_is_f32,
     else
         hipLaunchKernelGGL((dice_partial_kernel<uint8_t, MASKED>), dim3(kBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, n, classes, hw, workspace);
     VS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(64), 0, s, workspace, kBlocks, classes, eps, stats, loss);
+    hipLaunchKernelGGL(dice_finalize_kernel<WEIGHTED>, dim3(1), dim3(64), 0, s, (const float*)workspace, cw, kBlocks, classes, eps, stats, loss);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
 
-template <bool MASKED>
+template <bool MASKED, bool WEIGHTED = false>
 int dice_bwd_launch(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, const float* grad_out, int n,
-                    int classes, int64_t hw, float eps, const float* workspace, float* dlogits, hipStream_t s) {
+                    int classes, int64_t hw, float eps, const float* workspace, float* dlogits, hipStream_t s, const float* cw = nullptr) {
     const float* stats = workspace + (size_t)kBlocks * classes * 3;
     const int64_t total = (int64_t)n * classes * hw;
     const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
@@ -354,13 +362,13 @@ int dice_bwd_launch(const float* logits, const void* targets, int target_is_f32,
                       ((uintptr_t)targets & (target_is_f32 ? 15 : 3)) == 0 && (!MASKED || ((uintptr_t)valid & 3) == 0);
     const int grid4 = (int)std::min<int64_t>(4096, (total / 4 + 511) / 512);
     if (vec4 && target_is_f32)
-        hipLaunchKernelGGL((dice_grad4_kernel<float, MASKED>), dim3(grid4), dim3(256), 0, s, logits, (const float*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad4_kernel<float, MASKED, WEIGHTED>), dim3(grid4), dim3(256), 0, s, logits, (const float*)targets, valid, cw, stats, grad_out, eps, n, classes, hw, dlogits);
     else if (vec4)
-        hipLaunchKernelGGL((dice_grad4_kernel<uint8_t, MASKED>), dim3(grid4), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad4_kernel<uint8_t, MASKED, WEIGHTED>), dim3(grid4), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, cw, stats, grad_out, eps, n, classes, hw, dlogits);
     else if (target_is_f32)
-        hipLaunchKernelGGL((dice_grad_kernel<float, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const float*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad_kernel<float, MASKED, WEIGHTED>), dim3(grid), dim3(256), 0, s, logits, (const float*)targets, valid, cw, stats, grad_out, eps, n, classes, hw, dlogits);
     else
-        hipLaunchKernelGGL((dice_grad_kernel<uint8_t, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, stats, grad_out, eps, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((dice_grad_kernel<uint8_t, MASKED, WEIGHTED>), dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, cw, stats, grad_out, eps, n, classes, hw, dlogits);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
@@ -412,6 +420,32 @@ extern "C" int vs_dice_loss_bwd_masked(const float* logits, const void* targets,
     VS_REQUIRE(logits && targets && valid && workspace && dlogits, "dice_loss_bwd_masked: bad arguments");
     return dice_bwd_launch<true>(logits, targets, target_is_f32, valid, grad_out, n, classes, hw, eps, workspace, dlogits,
                                  (hipStream_t)stream);
+}
+
+// Per-class loss weights: one entry point for the masked and the unmasked case (valid may be null), the weights used as given.
+extern "C" int vs_dice_loss_fwd_weighted(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                                         const float* class_weights, int n, int classes, int64_t hw, float eps, float* loss,
+                                         float* workspace, size_t workspace_bytes, void* stream) {
+    VS_REQUIRE(class_weights, "dice_loss_fwd_weighted: class_weights is null (the unweighted call is vs_dice_loss_fwd)");
+    VS_REQUIRE(logits && targets && loss && workspace && classes >= 1, "dice_loss_fwd_weighted: bad arguments");
+    VS_REQUIRE(workspace_bytes >= vs_dice_workspace(classes), "dice_loss_fwd_weighted: workspace too small");
+    if (valid)
+        return dice_fwd_launch<true, true>(logits, targets, target_is_f32, valid, n, classes, hw, eps, loss, workspace, (hipStream_t)stream,
+                                           class_weights);
+    return dice_fwd_launch<false, true>(logits, targets, target_is_f32, nullptr, n, classes, hw, eps, loss, workspace, (hipStream_t)stream,
+                                        class_weights);
+}
+
+extern "C" int vs_dice_loss_bwd_weighted(const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                                         const float* class_weights, const float* grad_out, int n, int classes, int64_t hw, float eps,
+                                         const float* workspace, float* dlogits, void* stream) {
+    VS_REQUIRE(class_weights, "dice_loss_bwd_weighted: class_weights is null (the unweighted call is vs_dice_loss_bwd)");
+    VS_REQUIRE(logits && targets && workspace && dlogits && classes >= 1, "dice_loss_bwd_weighted: bad arguments");
+    if (valid)
+        return dice_bwd_launch<true, true>(logits, targets, target_is_f32, valid, grad_out, n, classes, hw, eps, workspace, dlogits,
+                                           (hipStream_t)stream, class_weights);
+    return dice_bwd_launch<false, true>(logits, targets, target_is_f32, nullptr, grad_out, n, classes, hw, eps, workspace, dlogits,
+                                        (hipStream_t)stream, class_weights);
 }
 
 extern "C" size_t vs_mean_iou_workspace(int n, int classes) { return (size_t)n * classes * 2 * sizeof(int); }
@@ -470,10 +504,12 @@ __device__ __forceinline__ float bce_elem(float x, float t) { return fmaxf(x, 0.
 
 // MASKED: block_valid[block] receives the number of valid pixels the block saw (counted in class 0's pass, in integers): their sum
 // is M, which the finalise uses where the unmasked form is handed n hw and n k hw by the host.
-template <typename TT, bool MASKED>
+// WEIGHTED: only the cross entropy (kind 3) differs here - its class-0 pass sums w_t l in slot 5 and w_t in slot 4, which kind 3
+// leaves unused; the other kinds keep their unweighted per-class sums and meet the weights in the finalise.
+template <typename TT, bool MASKED, bool WEIGHTED>
 __global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restrict__ x, const TT* __restrict__ t,
-                                                        const uint8_t* __restrict__ valid, int kind, int n, int k, int64_t hw,
-                                                        float* __restrict__ partial, int* __restrict__ block_valid) {
+                                                        const uint8_t* __restrict__ valid, const float* __restrict__ cw, int kind, int n,
+                                                        int k, int64_t hw, float* __restrict__ partial, int* __restrict__ block_valid) {
     __shared__ float red[kSegSums][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int seen = 0;
@@ -494,13 +530,19 @@ __global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restric
                         for (int q = 1; q < k; ++q) m = fmaxf(m, x[p0 + (size_t)q * hw]);
                         float se = 0.f;
                         bool found = false;
+                        [[maybe_unused]] int cls = 0;
                         for (int q = 0; q < k; ++q) {
                             const float xq = x[p0 + (size_t)q * hw];
                             se += expf(xq - m);
-                            if (!found && tval(t, p0 + (size_t)q * hw) != 0.f) { xt = xq; found = true; }   // first 1 = argmax of the one-hot
+                            if (!found && tval(t, p0 + (size_t)q * hw) != 0.f) { xt = xq; found = true; cls = q; }   // first 1 = argmax of the one-hot
                         }
                         if (!found) xt = x[p0];                                                                   // all-zero column: argmax = 0
-                        s[5] += (m + logf(se)) - xt;
+                        if constexpr (WEIGHTED) {
+                            const float wt = cw[cls];
+                            s[5] += wt * ((m + logf(se)) - xt); s[4] += wt;
+                        } else {
+                            s[5] += (m + logf(se)) - xt;
+                        }
                     }
                 } else {
                     const float p = sigmoidf_(xv);
@@ -533,10 +575,14 @@ __global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restric
 // one wave: per-class sums in fp64 (fixed order), the loss, and coef[c] = {a_c, b_c, g_c} + scal = {s}
 // MASKED: n_pix = M = the sum of block_valid and m_elems = M k replace the two arguments; with M = 0 the BCE and cross-entropy
 // terms and their gradient scale are 0 (not 0 / 0), the Dice terms follow their formulas (every D <= eps: loss 1).
-template <bool MASKED>
+// WEIGHTED (kinds 1 to 3): the BCE total is sum_c w_c BCE_c and wscale[c] = w_c wb / m_elems is the BCE gradient scale of class c,
+// in a table of its own behind the workspace of the masked form; a_c and b_c carry w_c; the cross entropy divides by the sum of
+// w_t (slot 4 of class 0) instead of the pixel count, and is 0 with a zero gradient when that sum is 0.
+template <bool MASKED, bool WEIGHTED>
 __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restrict__ partial, const int* __restrict__ block_valid,
-                                                        int nblocks, int kind, int k, double m_elems, double n_pix, float alpha,
-                                                        float beta, float eps, float* __restrict__ coef, float* __restrict__ loss) {
+                                                        const float* __restrict__ cw, int nblocks, int kind, int k, double m_elems,
+                                                        double n_pix, float alpha, float beta, float eps, float* __restrict__ coef,
+                                                        float* __restrict__ wscale, float* __restrict__ loss) {
     const int lane = threadIdx.x;
     __shared__ double S[16][kSegSums];
     [[maybe_unused]] const double all_pix = n_pix;
@@ -565,8 +611,17 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
     __syncthreads();
     if (lane != 0) return;
     double total = 0.0, bce = 0.0;
-    for (int c = 0; c < k; ++c) bce += S[c][5];
-    const bool none = MASKED && n_pix == 0.0;
+    if constexpr (WEIGHTED) {
+        if (kind == 3) {
+            bce = S[0][5];
+            n_pix = S[0][4];                                    // sum of w_t over the labelled pixels
+        } else {
+            for (int c = 0; c < k; ++c) bce += (double)cw[c] * S[c][5];
+        }
+    } else {
+        for (int c = 0; c < k; ++c) bce += S[c][5];
+    }
+    const bool none = (MASKED || WEIGHTED) && n_pix == 0.0;
     float* scal = coef + 16 * 4;
     scal[0] = 0.f;
     if constexpr (MASKED) scal[1] = 0.f;
@@ -575,16 +630,20 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
         const double wb = kind == 1 ? (double)alpha : 1.0;
         total += none ? 0.0 : wb * bce / m_elems;
         scal[0] = none ? 0.f : (float)(wb / m_elems);            // d/dx of the mean BCE: (p - t) / M
+        if constexpr (WEIGHTED) {
+            for (int c = 0; c < 16; ++c) wscale[c] = (none || c >= k) ? 0.f : (float)((double)cw[c] * (wb / m_elems));
+        }
         if (kind == 1) {
             double acc = 0.0;
             for (int c = 0; c < k; ++c) {
                 const double I = S[c][0], D = S[c][1] + S[c][2];
                 const bool big = D > (double)eps;
                 const double Dc = big ? D : (double)eps;
-                acc += 2.0 * I / Dc;
+                const double w = WEIGHTED ? (double)cw[c] : 1.0;
+                acc += w * (2.0 * I / Dc);
                 // d(1 - mean_c 2 I / D)/dp = -(2/K) (t D - 2 p I) / D^2 ; with D clamped: -(2/K) t / eps
-                coef[c * 4 + 0] = (float)(beta * (-2.0 / k) / Dc);
-                coef[c * 4 + 1] = big ? (float)(beta * (4.0 / k) * I / (D * D)) : 0.f;
+                coef[c * 4 + 0] = (float)(w * (beta * (-2.0 / k) / Dc));
+                coef[c * 4 + 1] = big ? (float)(w * (beta * (4.0 / k) * I / (D * D))) : 0.f;
             }
             total += beta * (1.0 - acc / k);
         }
@@ -628,9 +687,11 @@ __global__ __launch_bounds__(64) void seg_finalize_kernel(const float* __restric
     *loss = (float)total;
 }
 
-template <typename TT, bool MASKED>
+// WEIGHTED: the BCE scale of an element is wscale[class] (kinds 1, 2); the cross-entropy scale of a pixel is w_cls / sum w_t
+template <typename TT, bool MASKED, bool WEIGHTED>
 __global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__ x, const TT* __restrict__ t,
-                                                     const uint8_t* __restrict__ valid, const float* __restrict__ coef,
+                                                     const uint8_t* __restrict__ valid, const float* __restrict__ cw,
+                                                     const float* __restrict__ coef, const float* __restrict__ wscale,
                                                      const float* __restrict__ gout, int kind, int n, int k, int64_t hw,
                                                      float* __restrict__ dx) {
     const float g = gout ? *gout : 1.f;
@@ -655,8 +716,9 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__
                 se += expf(x[p0 + (size_t)q * hw] - m);
                 if (!found && tval(t, p0 + (size_t)q * hw) != 0.f) { cls = q; found = true; }
             }
+            const float gs = WEIGHTED ? g * sc * cw[cls] : g * sc;
             for (int q = 0; q < k; ++q)
-                dx[p0 + (size_t)q * hw] = g * sc * (expf(x[p0 + (size_t)q * hw] - m) / se - (q == cls ? 1.f : 0.f));
+                dx[p0 + (size_t)q * hw] = gs * (expf(x[p0 + (size_t)q * hw] - m) / se - (q == cls ? 1.f : 0.f));
         }
         return;
     }
@@ -678,7 +740,7 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__
         const float xv = x[i], tv = tval(t, i);
         const float p = sigmoidf_(xv);
         const float dldp = coef[c * 4 + 0] * tv + coef[c * 4 + 1] * p + coef[c * 4 + 2];
-        const float d = g * (dldp * p * (1.f - p) + sc * (p - tv));
+        const float d = g * (dldp * p * (1.f - p) + (WEIGHTED ? wscale[c] : sc) * (p - tv));
         // the value is formed for every element and selected at the end: a loop body of the unmasked shape, which the compiler
         // unrolls and contracts as it does the unmasked one (an early `continue` here gave other roundings in the unrolled trips)
         if constexpr (MASKED) dx[i] = valid[(size_t)(plane / k) * hw + (i - plane * hw)] ? d : 0.f;
@@ -686,33 +748,36 @@ __global__ __launch_bounds__(256) void seg_grad_kernel(const float* __restrict__
     }
 }
 
-// workspace: partial sums, coef[16 * 4], scal[4] and - the masked form only - one int per block of the reduction
-template <bool MASKED>
+// workspace: partial sums, coef[16 * 4], scal[4], - the masked form and the weighted one - one int per block of the reduction and
+// - the weighted form only - wscale[16]
+template <bool MASKED, bool WEIGHTED = false>
 int seg_fwd_launch(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, int n, int classes,
-                   int64_t hw, float alpha, float beta, float eps, float* loss, float* workspace, hipStream_t s) {
+                   int64_t hw, float alpha, float beta, float eps, float* loss, float* workspace, hipStream_t s, const float* cw = nullptr) {
     float* coef = workspace + (size_t)kSegBlocks * classes * kSegSums;
     int* block_valid = (int*)(coef + 16 * 4 + 4);
+    float* wscale = (float*)(block_valid + kSegBlocks);      // WEIGHTED only: the other workspaces end before it
     if (target_is_f32)
-        hipLaunchKernelGGL((seg_partial_kernel<float, MASKED>), dim3(kSegBlocks), dim3(256), 0, s, logits, (const float*)targets, valid, kind, n, classes, hw, workspace, block_valid);
+        hipLaunchKernelGGL((seg_partial_kernel<float, MASKED, WEIGHTED>), dim3(kSegBlocks), dim3(256), 0, s, logits, (const float*)targets, valid, cw, kind, n, classes, hw, workspace, block_valid);
     else
-        hipLaunchKernelGGL((seg_partial_kernel<uint8_t, MASKED>), dim3(kSegBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, kind, n, classes, hw, workspace, block_valid);
+        hipLaunchKernelGGL((seg_partial_kernel<uint8_t, MASKED, WEIGHTED>), dim3(kSegBlocks), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, cw, kind, n, classes, hw, workspace, block_valid);
     VS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(seg_finalize_kernel<MASKED>, dim3(1), dim3(64), 0, s, workspace, (const int*)block_valid, kSegBlocks, kind, classes,
-                       (double)n * classes * (double)hw, (double)n * (double)hw, alpha, beta, eps, coef, loss);
+    hipLaunchKernelGGL((seg_finalize_kernel<MASKED, WEIGHTED>), dim3(1), dim3(64), 0, s, (const float*)workspace, (const int*)block_valid, cw,
+                       kSegBlocks, kind, classes, (double)n * classes * (double)hw, (double)n * (double)hw, alpha, beta, eps, coef, wscale, loss);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
 
-template <bool MASKED>
+template <bool MASKED, bool WEIGHTED = false>
 int seg_bwd_launch(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid, const float* grad_out,
-                   int n, int classes, int64_t hw, const float* workspace, float* dlogits, hipStream_t s) {
+                   int n, int classes, int64_t hw, const float* workspace, float* dlogits, hipStream_t s, const float* cw = nullptr) {
     const float* coef = workspace + (size_t)kSegBlocks * classes * kSegSums;
+    const float* wscale = coef + 16 * 4 + 4 + kSegBlocks;
     const int64_t total = kind == 3 ? (int64_t)n * hw : (int64_t)n * classes * hw;
     const int grid = (int)std::min<int64_t>(8192, (total + 255) / 256);
     if (target_is_f32)
-        hipLaunchKernelGGL((seg_grad_kernel<float, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const float*)targets, valid, coef, grad_out, kind, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((seg_grad_kernel<float, MASKED, WEIGHTED>), dim3(grid), dim3(256), 0, s, logits, (const float*)targets, valid, cw, coef, wscale, grad_out, kind, n, classes, hw, dlogits);
     else
-        hipLaunchKernelGGL((seg_grad_kernel<uint8_t, MASKED>), dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, coef, grad_out, kind, n, classes, hw, dlogits);
+        hipLaunchKernelGGL((seg_grad_kernel<uint8_t, MASKED, WEIGHTED>), dim3(grid), dim3(256), 0, s, logits, (const uint8_t*)targets, valid, cw, coef, wscale, grad_out, kind, n, classes, hw, dlogits);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
@@ -721,6 +786,7 @@ int seg_bwd_launch(int kind, const float* logits, const void* targets, int targe
 
 extern "C" size_t vs_seg_loss_workspace(int classes) { return ((size_t)kSegBlocks * classes * kSegSums + 16 * 4 + 4) * sizeof(float); }
 extern "C" size_t vs_seg_loss_masked_workspace(int classes) { return vs_seg_loss_workspace(classes) + kSegBlocks * sizeof(int); }
+extern "C" size_t vs_seg_loss_weighted_workspace(int classes) { return vs_seg_loss_masked_workspace(classes) + 16 * sizeof(float); }
 
 extern "C" int vs_seg_loss_fwd(int kind, const float* logits, const void* targets, int target_is_f32, int n, int classes, int64_t hw,
                                float alpha, float beta, float eps, float* loss, float* workspace, size_t workspace_bytes, void* stream) {
@@ -755,4 +821,35 @@ extern "C" int vs_seg_loss_bwd_masked(int kind, const float* logits, const void*
     VS_REQUIRE(kind >= 1 && kind <= 4 && logits && targets && valid && workspace && dlogits, "seg_loss_bwd_masked: bad arguments");
     return seg_bwd_launch<true>(kind, logits, targets, target_is_f32, valid, grad_out, n, classes, hw, workspace, dlogits,
                                 (hipStream_t)stream);
+}
+
+// Per-class loss weights for kinds 1 to 3 (the generalised Dice has its own inverse-volume weights: kind 4 is refused).  One entry
+// point for the masked and the unmasked case (valid may be null); the weights are used as given.
+extern "C" int vs_seg_loss_fwd_weighted(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                                        const float* class_weights, int n, int classes, int64_t hw, float alpha, float beta, float eps,
+                                        float* loss, float* workspace, size_t workspace_bytes, void* stream) {
+    VS_REQUIRE(kind >= 1 && kind <= 3, "seg_loss_fwd_weighted: kind must be 1 (BCE-Dice), 2 (BCE) or 3 (cross entropy); the generalised "
+                                       "Dice (4) takes no class weights");
+    VS_REQUIRE(class_weights, "seg_loss_fwd_weighted: class_weights is null (the unweighted call is vs_seg_loss_fwd)");
+    VS_REQUIRE(logits && targets && loss && workspace && classes >= 1 && classes <= 16, "seg_loss_fwd_weighted: bad arguments");
+    VS_REQUIRE(workspace_bytes >= vs_seg_loss_weighted_workspace(classes), "seg_loss_fwd_weighted: workspace too small");
+    if (valid)
+        return seg_fwd_launch<true, true>(kind, logits, targets, target_is_f32, valid, n, classes, hw, alpha, beta, eps, loss, workspace,
+                                          (hipStream_t)stream, class_weights);
+    return seg_fwd_launch<false, true>(kind, logits, targets, target_is_f32, nullptr, n, classes, hw, alpha, beta, eps, loss, workspace,
+                                       (hipStream_t)stream, class_weights);
+}
+
+extern "C" int vs_seg_loss_bwd_weighted(int kind, const float* logits, const void* targets, int target_is_f32, const uint8_t* valid,
+                                        const float* class_weights, const float* grad_out, int n, int classes, int64_t hw,
+                                        const float* workspace, float* dlogits, void* stream) {
+    VS_REQUIRE(kind >= 1 && kind <= 3, "seg_loss_bwd_weighted: kind must be 1 (BCE-Dice), 2 (BCE) or 3 (cross entropy); the generalised "
+                                       "Dice (4) takes no class weights");
+    VS_REQUIRE(class_weights, "seg_loss_bwd_weighted: class_weights is null (the unweighted call is vs_seg_loss_bwd)");
+    VS_REQUIRE(logits && targets && workspace && dlogits && classes >= 1 && classes <= 16, "seg_loss_bwd_weighted: bad arguments");
+    if (valid)
+        return seg_bwd_launch<true, true>(kind, logits, targets, target_is_f32, valid, grad_out, n, classes, hw, workspace, dlogits,
+                                          (hipStream_t)stream, class_weights);
+    return seg_bwd_launch<false, true>(kind, logits, targets, target_is_f32, nullptr, grad_out, n, classes, hw, workspace, dlogits,
+                                       (hipStream_t)stream, class_weights);
 }

@@ -160,6 +160,20 @@ class TrainingDataSlicer(BaseDataManager):
         self.seg_vol = relabelled
         self.codes = [f"label_val_{i}" for i in seg_classes]
 
+    @property
+    def class_counts(self) -> np.ndarray:
+        """Labelled voxels per relabelled class 0 .. K-1 (int64; the unlabelled value 255 of sparse labels is not counted): one
+        np.bincount over the volume, taken when first asked for (``loss_class_weights: balanced``) and kept."""
+        if getattr(self, "_class_counts", None) is None:
+            flat = np.asarray(self.seg_vol).reshape(-1)
+            if flat.dtype.kind not in "ui":
+                flat = flat.astype(np.int64)
+            counts = np.bincount(flat, minlength=self.num_seg_classes)
+            if self.ignore_label is not None:
+                counts = counts[:utils.IGNORE_INDEX]
+            self._class_counts = counts[:self.num_seg_classes].astype(np.int64)
+        return self._class_counts
+
     def labelled_slices(self, axis: str) -> np.ndarray:
         """Per slice along ``axis`` ('z', 'y', 'x'): whether it holds a value other than 255.  All true without an ignore label."""
         n = self.seg_vol.shape["zyx".index(axis)]

@@ -30,13 +30,33 @@ import torch.nn as nn
 from ... import dist as vdist
 from ...checkpoint_compat import reference_pickle_enum
 from ...data.datasets import get_2d_training_dataloaders
-from ...data.losses import (BCEDiceLoss, DiceCoefficient, DiceLoss, GeneralizedDiceLoss, HipDiceLoss, HipSegLoss, MeanIoU,
-                            masked_criterion)
+from ...data.losses import (CLASS_WEIGHTS_KEY, BCEDiceLoss, DiceCoefficient, DiceLoss, GeneralizedDiceLoss, HipDiceLoss, HipSegLoss,
+                            MeanIoU, class_weight_tensor, class_weights_from_counts, masked_criterion, resolve_class_weights)
 from ...engine import FusedAdamW, VolSegUnet
 from ...utilities import base_data_utils as utils
 from ...utilities import config as cfg
 from ...utilities.early_stopping import EarlyStopping
 from ..model_2d import create_model_on_device
+
+
+def resolve_balanced_class_weights(settings: SimpleNamespace, slicers, num_classes: int) -> SimpleNamespace:
+    """``loss_class_weights: balanced`` -> the list w_c = N / (K n_c), from the labelled voxels per class summed over the label
+    volumes of ``slicers`` (TrainingDataSlicer.class_counts).  Returns the settings to build the trainer with: a copy that holds the
+    list where the key says ``balanced``, the settings themselves otherwise."""
+    spec = getattr(settings, CLASS_WEIGHTS_KEY, None)
+    if not (isinstance(spec, str) and spec.strip().lower() == "balanced"):
+        return settings
+    counts = np.zeros(num_classes, dtype=np.int64)
+    for slicer in slicers:
+        own = np.asarray(slicer.class_counts)
+        if own.size > num_classes:
+            raise ValueError(f"{CLASS_WEIGHTS_KEY}: balanced: a label volume holds {own.size} classes, the run has {num_classes}")
+        counts[:own.size] += own
+    weights = class_weights_from_counts(counts, num_classes)
+    logging.info(f"{CLASS_WEIGHTS_KEY}: balanced: labelled voxels per class {counts.tolist()}")
+    resolved = SimpleNamespace(**vars(settings))
+    setattr(resolved, CLASS_WEIGHTS_KEY, weights)
+    return resolved
 
 
 class VolSeg2dTrainer:
@@ -59,6 +79,9 @@ class VolSeg2dTrainer:
         # relabels), and the loss and the metric then see a validity mask next to the one-hot targets
         self.ignore_label = utils.IGNORE_INDEX if getattr(settings, "ignore_label", None) is not None else None
         self._graph_declined = False
+        # per-class loss weights: None without the key - then nothing below differs from a run without the feature
+        self.class_weights = resolve_class_weights(getattr(settings, CLASS_WEIGHTS_KEY, None), self.label_no,
+                                                   getattr(settings, "loss_criterion", None))
         self.starting_lr, self.end_lr = float(settings.starting_lr), float(settings.end_lr)
         self.log_lr_ratio = self._calculate_log_lr_ratio()
         self.lr_find_epochs = settings.lr_find_epochs
@@ -91,6 +114,7 @@ class VolSeg2dTrainer:
         (data directory, label directory) after all and the PNG route is taken."""
         from ...data.volume_feed import get_volume_training_loaders
         slicers = list(slicers)
+        settings = resolve_balanced_class_weights(settings, slicers, labels if isinstance(labels, int) else len(labels))
         vdist.init_from_env()
         rank, world = vdist.world()
         loaders = get_volume_training_loaders(slicers, settings, rank, world)
@@ -123,6 +147,8 @@ class VolSeg2dTrainer:
     def _get_loss_criterion(self):
         name = self.settings.loss_criterion
         gpu = torch.cuda.is_available()     # fused HIP sweeps on device tensors; the torch restatements otherwise
+        if self.class_weights is not None:
+            return self._get_weighted_loss_criterion(name, gpu, class_weight_tensor(self.class_weights))
         if name == "BCEDiceLoss":
             return HipSegLoss(name, self.settings.alpha, self.settings.beta) if gpu else BCEDiceLoss(self.settings.alpha, self.settings.beta)
         if name == "DiceLoss":
@@ -136,6 +162,25 @@ class VolSeg2dTrainer:
             return HipSegLoss(name) if gpu else nn.CrossEntropyLoss()
         if name == "GeneralizedDiceLoss":
             return HipSegLoss(name) if gpu else GeneralizedDiceLoss()
+        logging.error("No loss criterion specified, exiting")
+        sys.exit(1)
+
+    def _get_weighted_loss_criterion(self, name, gpu, w):
+        """the criteria of _get_loss_criterion with the resolved ``loss_class_weights`` (the metric is never weighted)"""
+        if name == "BCEDiceLoss":
+            alpha, beta = self.settings.alpha, self.settings.beta
+            return HipSegLoss(name, alpha, beta, weight=w) if gpu else BCEDiceLoss(alpha, beta, weight=w)
+        if name == "DiceLoss":
+            if gpu and self.world > 1 and bool(getattr(self.settings, "sync_batchnorm", False)):
+                import torch.distributed as dist
+                return HipDiceLoss(global_group=dist.group.WORLD, weight=w)
+            return HipDiceLoss(weight=w) if gpu else DiceLoss(weight=w, normalization="none")
+        if name == "BCELoss":
+            return HipSegLoss(name, weight=w) if gpu else nn.BCEWithLogitsLoss(weight=w.view(1, -1, 1, 1))
+        if name == "CrossEntropyLoss":
+            return HipSegLoss(name, weight=w) if gpu else nn.CrossEntropyLoss(weight=w)
+        if name == "GeneralizedDiceLoss":
+            raise ValueError(f"{CLASS_WEIGHTS_KEY}: GeneralizedDiceLoss has its own inverse-volume class weights and takes none")
         logging.error("No loss criterion specified, exiting")
         sys.exit(1)
 
@@ -239,9 +284,10 @@ class VolSeg2dTrainer:
         # ran 2 - 4 % faster (4.65 vs 4.82 ms; the replay's range boundaries cost more than a host that keeps up) - for a slow or busy
         # host the replay is the one to pick (bench.py times both and keeps the faster)
         fuse = getattr(self.model, "can_fuse_step", None) if getattr(self.settings, "step_mode", "eager") == "graph" else None
-        if fuse is not None and valid is not None:     # the recorded step has no masked form: enqueue call by call
+        if fuse is not None and (valid is not None or self.class_weights is not None):     # the recorded step has no masked and no weighted form: enqueue call by call
             if not self._graph_declined:
-                logging.info("step_mode: graph is not available with an ignore_label: the step is enqueued call by call.")
+                what = "an ignore_label" if valid is not None else CLASS_WEIGHTS_KEY
+                logging.info(f"step_mode: graph is not available with {what}: the step is enqueued call by call.")
                 self._graph_declined = True
             fuse = None
         if fuse is not None and isinstance(self.loss_criterion, HipDiceLoss) and fuse(self.optimizer, inputs, targets):
@@ -345,6 +391,7 @@ class VolSeg2dTrainer:
 
     _epochs_run = 0
     _aug_rng = None
+    class_weights = None      # the resolved `loss_class_weights` (set by __init__); None: no weights
 
     def _lr_finder(self, lr_scheduler, smoothing=0.05):
         losses, lrs, iters = [], [], 0

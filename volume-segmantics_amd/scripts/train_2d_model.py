@@ -41,7 +41,7 @@ def main(argv=None) -> None:
     if feed == "volume" and not volume_feed_applies(settings):
         logging.error("slice_feed: volume needs a GPU and device-side augmentation (image_size a multiple of 8, augment not 'host').")
         sys.exit(1)
-    from ..model.operations.vol_seg_2d_trainer import VolSeg2dTrainer
+    from ..model.operations.vol_seg_2d_trainer import VolSeg2dTrainer, resolve_balanced_class_weights
     vdist.init_from_env()
     rank, _world = vdist.world()
     data_dir, seg_dir = root / settings.data_im_dirname, root / settings.seg_im_out_dirname
@@ -49,6 +49,7 @@ def main(argv=None) -> None:
     check_ignore_label_occurs(slicers)
     widest = max(slicers, key=lambda s: s.num_seg_classes)      # (the first of equals, as the reference's loop keeps it)
     max_label_no, label_codes = widest.num_seg_classes, widest.codes
+    settings = resolve_balanced_class_weights(settings, slicers, max_label_no)      # `loss_class_weights: balanced` -> the list
     if feed == "volume":
         trainer = VolSeg2dTrainer.from_volumes(slicers, max_label_no, settings, png_dirs=(data_dir, seg_dir))
     else:
