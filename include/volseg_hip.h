@@ -156,6 +156,10 @@ int vs_stem_fwd(int dtype, const float* x, const float* w, const float* scale, c
 int vs_stem_wgrad(int dtype, const float* x, const void* dy, float* dw, float* workspace, size_t workspace_bytes,
                   int n, int h, int w_, void* stream);
 size_t vs_stem_wgrad_workspace(int n, int h, int w_);
+/* vs_stem_fwd (bf16, option "stem_bf16", no epilogue) that also leaves the batch statistics of z in bins: [nb][2][64] 64-bit fixed-point
+ * sums (sum z * vs_stat_scale(0), sum z^2 * vs_stat_scale(1)) of the fp32 accumulators over the valid output pixels, added to what the
+ * caller zeroed; nb a power of two.  VS_ERR_UNSUPPORTED for any other dtype or with the option off. */
+int vs_stem_fwd_bins(int dtype, const float* x, const float* w, void* z, int n, int h, int w_, unsigned long long* bins, int nb, void* stream);
 
 /* Train-mode BatchNorm2d (eps 1e-5, momentum 0.1, biased batch var, unbiased running var) on
  * x: [rows][c].  stats: mean[c], invstd[c]; running stats updated in place when not null. */

@@ -6,8 +6,9 @@ the figure (measured error over bound) a test asserts to be at most 1.
 Covered: launch_conv_igemm's forward launch - every tile instantiation of launch_tile without normalise-on-load, the ring kernel's
 three modes, the persistent stream kernel at both cout tiles, the direct strip kernel and the head kernel - with the loader forms
 (nearest x2 + concatenation, zero stuffing, dilation) and the epilogue forms (affine, shift, residual, ReLU, fp32 / NCHW store, 2 x 2
-sum-pool, split output).  The weight gradients have their own table of this kind, tests/wgrad_cases.py.  Not covered here: the
-BatchNorm-backward epilogue (bz), normalise-on-load, swish, the stem, grouped and depthwise forms; they keep their own tests.
+sum-pool, split output).  The weight gradients have their own table of this kind, tests/wgrad_cases.py, and so has the stem
+(csrc/stem.hip, forward and weight gradient), tests/stem_cases.py.  Not covered here: the BatchNorm-backward epilogue (bz),
+normalise-on-load, swish, grouped and depthwise forms; they keep their own tests.
 
 The bound, per output element.  U = 2^-24 is the unit roundoff of fp32, gamma_m = m U / (1 - m U) bounds m roundings in a row.  The
 inputs are fp32 values the storage type holds exactly, so no input rounding is charged.  Every later term is taken on the magnitude

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_cases as CC
+import stem_cases as SC
 import wgrad_cases as WC
 from hip_helpers import (DEV, conv_desc, from_nhwc, lib, rounded, sync, tdtype, to_nhwc, tol, w_krsc)
 
@@ -750,12 +751,17 @@ def test_stem_fwd_and_wgrad(code):
     L.check(L.lib.vs_stem_fwd(code, L.ptr(xd), L.ptr(wd), None, None, 0, L.ptr(out), n, h, w, None))
     sync()
     assert torch.allclose(from_nhwc(out), y.detach(), **tol(code, y.abs().max().item()))
+    # and within the per-element bounds of tests/stem_cases.py, against float64 on the operands the kernels' arithmetic sees (default options:
+    # bf16 runs the MFMA-16 kernels, which round the image and the weights while staging)
+    xs, wts, mfma16 = rounded(x, code), rounded(wt0, code), code == 1
+    figs = [SC.figure_against(from_nhwc(out), *SC.fwd_reference_and_bound(xs, wts, mfma16, code))]
     sc, sh = torch.rand(64) + 0.5, torch.randn(64)
     scd, shd = sc.to(DEV), sh.to(DEV)
     L.check(L.lib.vs_stem_fwd(code, L.ptr(xd), L.ptr(wd), L.ptr(scd), L.ptr(shd), 1, L.ptr(out), n, h, w, None))
     sync()
     ref = (y.detach() * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)).relu()
     assert torch.allclose(from_nhwc(out), ref, **tol(code, ref.abs().max().item()))
+    figs.append(SC.figure_against(from_nhwc(out), *SC.fwd_reference_and_bound(xs, wts, mfma16, code, sc, sh, 1)))
     wsb = L.lib.vs_stem_wgrad_workspace(n, h, w)
     ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
     dw = torch.full((64, 49), float("nan"), device=DEV)
@@ -763,6 +769,10 @@ def test_stem_fwd_and_wgrad(code):
     sync()
     ref_dw = wt.grad.reshape(64, 49)
     assert torch.allclose(dw.cpu(), ref_dw, rtol=1e-3, atol=1e-3 * ref_dw.abs().max().item())
+    per, ranges, _ = SC.range_structure(SC.tile_count(n, h, w), SC.WGRAD_BLOCKS["wgrad-mfma16" if mfma16 else "wgrad"])      # 16 tiles: 16 ranges of one
+    figs.append(SC.figure_against(dw.cpu(), *SC.wgrad_reference_and_bound(xs, dy, mfma16, per, ranges, SC.slab_group(ranges))))
+    print(f"stem {CC.DT[code]} {(n, h, w)}: forward {figs[0]:.3g}, affine + ReLU {figs[1]:.3g}, weight gradient {figs[2]:.3g} of the bound")
+    assert all(f <= 1.0 for f in figs), figs
 
 
 @pytest.mark.parametrize("code", CODES)

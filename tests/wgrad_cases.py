@@ -8,8 +8,9 @@ are those of tests/conv_cases.py.
 Covered: the generic kernel (fp32, and bf16 where cout is no multiple of 8), the bf16 fast kernel, the ring kernel in its four forms,
 the three row-streaming kernels at their three widths, the four slab-reduce kernels and the grouped extract; with the loader forms
 (nearest x2 + concatenation, dilation 2 / 4, both stride-2 tile shapes), the split structure (one split, two tiles per split, a
-shorter last split, the three workgroup assignment modes, every reduce group) and the launches that must be refused.  Not covered
-here: the stem and depthwise weight gradients, which keep their own tests.
+shorter last split, the three workgroup assignment modes, every reduce group) and the launches that must be refused.  The stem's
+weight gradient (csrc/stem.hip) has its own table of this kind, tests/stem_cases.py.  Not covered here: the depthwise weight gradients,
+which keep their own tests.
 
 The bound, per element of dw.  U = 2^-24 is the unit roundoff of fp32, gamma_m = m U / (1 - m U) bounds m roundings in a row.  The
 inputs are fp32 values the storage type holds exactly and every product of two of them is exact in fp32 (16-bit operands) or rounded

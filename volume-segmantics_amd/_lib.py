@@ -157,6 +157,7 @@ _SIGS = {
     "vs_colsum": (I, [I, P, C.c_int64, I, P, P, SZ, P]),
     "vs_stem_fwd": (I, [I, P, P, P, P, I, P, I, I, I, P]),
     "vs_stem_wgrad": (I, [I, P, P, P, P, SZ, I, I, I, P]),
+    "vs_stem_fwd_bins": (I, [I, P, P, P, I, I, I, P, I, P]),
     "vs_stem_wgrad_workspace": (SZ, [I, I, I]),
     "vs_bn_stats": (I, [I, P, I64, I, F, F, P, P, P, P, P, SZ, P]),
     "vs_bn_workspace": (SZ, [I64, I]),

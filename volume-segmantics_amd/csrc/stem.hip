@@ -471,14 +471,6 @@ __global__ __launch_bounds__(256) void stem_wgrad_bf16_kernel(const float* __res
     }
 }
 
-__global__ void stem_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dw, int nparts) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 64 * 49) return;
-    float s = 0.f;
-    for (int k = 0; k < nparts; ++k) s += partial[(size_t)k * 64 * 49 + i];
-    dw[i] = s;
-}
-
 constexpr int kStemBlocks = 1024;
 
 }  // namespace
@@ -513,6 +505,13 @@ int launch_stem_fwd_bins(const float* x, const float* w, void* z, int n, int h, 
                        (bf16_t*)z, n, h, w_, bins, nb);
     VS_LAUNCH_CHECK();
     return VS_OK;
+}
+
+// the same launch through the C ABI: what the unit's forward runs under default bf16 training (unet.hip calls the launcher itself)
+extern "C" int vs_stem_fwd_bins(int dtype, const float* x, const float* w, void* z, int n, int h, int w_, unsigned long long* bins, int nb,
+                                void* stream) {
+    if (!stem_fwd_bins_ok(dtype)) { vs_set_error("stem_fwd_bins: bf16 with option stem_bf16 only"); return VS_ERR_UNSUPPORTED; }
+    return launch_stem_fwd_bins(x, w, z, n, h, w_, bins, nb, (hipStream_t)stream);
 }
 
 extern "C" size_t vs_stem_wgrad_workspace(int n, int h, int w_) {
