@@ -843,6 +843,13 @@ int vs_label_surface(const uint8_t* labels, const uint8_t* lut, int cls, int64_t
 size_t vs_edt_workspace_bytes(int64_t Z, int64_t Y, int64_t X);
 int vs_edt_squared(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, uint32_t* d2, void* workspace, size_t workspace_bytes,
                    void* stream);
+/* vs_edt_squared_scaled: the same transform on a grid whose steps along z, y, x are the integer weights wz, wy, wx: d2[v] = the
+ * least qz dz^2 + qy dy^2 + qx dx^2 to a non-zero voxel of seeds, q = w^2 - an integer again, so a physical distance is
+ * unit * sqrt(d2) for a spacing of (wz, wy, wx) * unit.  Every weight is 1..64 and qz (Z-1)^2 + qy (Y-1)^2 + qx (X-1)^2 < 2^32 - 1
+ * (otherwise VS_ERR_INVALID, before any launch); an axis of length 1 contributes nothing.  Weights (1, 1, 1) give the bits of
+ * vs_edt_squared, (k, k, k) give k^2 times them.  The workspace is that of vs_edt_workspace_bytes. */
+int vs_edt_squared_scaled(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, uint32_t* d2, void* workspace,
+                          size_t workspace_bytes, void* stream);
 /* vs_surface_distance_histogram: hist[min(d2[v], bins - 1)] += 1 for every v < n with from_surface[v] != 0.  hist (bins int64)
  * is zeroed by the call; integer sums, the same bits in any arrival order.  from_surface 4-byte, d2 16-byte aligned. */
 int vs_surface_distance_histogram(const uint8_t* from_surface, const uint32_t* d2, int64_t n, int64_t bins, int64_t* hist,
@@ -1029,6 +1036,21 @@ int vs_thickness_paint(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const
                        int64_t max_r, void* workspace, size_t workspace_bytes, int zero_first, void* stream);
 int vs_thickness_resolve(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int64_t max_r, void* workspace,
                          size_t workspace_bytes, uint32_t* t2, void* stream);
+/* The same on a grid whose steps along z, y, x are the integer weights wz, wy, wx (1..64 each, and the extents
+ * vs_edt_squared_scaled takes; otherwise VS_ERR_INVALID, 0 bytes from the size query): r comes from vs_edt_squared_scaled, the ball
+ * of v is { u : D(u - v) < r[v] } with D(d) = qz dz^2 + qy dy^2 + qx dx^2, q = w^2.  A ball reaches isqrt((r - 1) / qz) planes and
+ * isqrt((r - 1) / qy) lines, its row (dz, dy) has m = r - qz dz^2 - qy dy^2 >= 1 and the half width isqrt((m - 1) / qx), and the level
+ * count follows the longest span 2 isqrt((max_r - 1) / qx) + 1.  need has SEVEN rows of need_len uint32, one per non-empty set of
+ * axes on which n - v is non-zero, row 4 [z] + 2 [y] + [x] - 1:  need[row][r] = 1 + max { D(p) + sum over the set of q_i (2 |p_i| + 1) :
+ * p in Z^3, D(p) < r }.  With weights (1, 1, 1) the results are those of the unscaled entry points. */
+size_t vs_thickness_workspace_bytes_scaled(int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, int64_t max_r);
+int vs_thickness_centres_scaled(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, const uint32_t* need,
+                                int64_t need_len, int32_t* centres, int64_t capacity, int64_t* totals, void* stream);
+int vs_thickness_paint_scaled(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, const int32_t* centres,
+                              int64_t count, int64_t largest_r, int64_t max_r, void* workspace, size_t workspace_bytes, int zero_first,
+                              void* stream);
+int vs_thickness_resolve_scaled(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, int value, int64_t max_r,
+                                void* workspace, size_t workspace_bytes, uint32_t* t2, void* stream);
 
 #ifdef __cplusplus
 }

@@ -269,6 +269,7 @@ _SIGS = {
     "vs_label_surface": (I, [P, P, I, I64, I64, I64, P, P, P]),
     "vs_edt_workspace_bytes": (SZ, [I64, I64, I64]),
     "vs_edt_squared": (I, [P, I64, I64, I64, P, P, SZ, P]),
+    "vs_edt_squared_scaled": (I, [P, I64, I64, I64, I, I, I, P, P, SZ, P]),
     "vs_surface_distance_histogram": (I, [P, P, I64, I64, P, P]),
     "vs_components_workspace_bytes": (SZ, [I64, I64, I64]),
     "vs_label_components": (I, [P, I64, I64, I64, I, P, P, SZ, P]),
@@ -292,6 +293,10 @@ _SIGS = {
     "vs_thickness_centres": (I, [P, I64, I64, I64, P, I64, P, I64, P, P]),
     "vs_thickness_paint": (I, [P, I64, I64, I64, P, I64, I64, I64, P, SZ, I, P]),
     "vs_thickness_resolve": (I, [P, I64, I64, I64, I, I64, P, SZ, P, P]),
+    "vs_thickness_workspace_bytes_scaled": (SZ, [I64, I64, I64, I, I, I, I64]),
+    "vs_thickness_centres_scaled": (I, [P, I64, I64, I64, I, I, I, P, I64, P, I64, P, P]),
+    "vs_thickness_paint_scaled": (I, [P, I64, I64, I64, I, I, I, P, I64, I64, I64, P, SZ, I, P]),
+    "vs_thickness_resolve_scaled": (I, [P, I64, I64, I64, I, I, I, I, I64, P, SZ, P, P]),
     "vs_augment_workspace": (SZ, [I, I]),
     "vs_augment_batch": (I, [P, P, I, I, P, P, P, P, P, P, SZ, P, P]),
     "vs_slices_cut_u8": (I, [P, I64, P, I64, P, I, I, P, P, P]),

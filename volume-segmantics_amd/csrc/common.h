@@ -206,6 +206,16 @@ inline int device_cus() {
 inline int persistent_workgroups() { return device_cus() * 8; }
 
 // a label volume's extents: each at least 1, and the Z x Y x X voxels (pad 0) or the (Z+1)(Y+1)(X+1) cells (pad 1) below 2^31
+// weights 1..64, axes of at most 65536 and qz (Z-1)^2 + qy (Y-1)^2 + qx (X-1)^2 < 2^32 - 1, q = w^2: every weighted squared distance in
+// the volume is a uint32 below the "no seed" mark (vs_edt_squared_scaled, vs_thickness_*_scaled).  An axis of length 1 contributes nothing.
+inline bool weighted_distances_fit(int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx) {
+    if (wz < 1 || wy < 1 || wx < 1 || wz > 64 || wy > 64 || wx > 64) return false;
+    if (Z < 1 || Y < 1 || X < 1 || Z > 65536 || Y > 65536 || X > 65536) return false;
+    const uint64_t s = (uint64_t)(wz * wz) * (uint64_t)((Z - 1) * (Z - 1)) + (uint64_t)(wy * wy) * (uint64_t)((Y - 1) * (Y - 1)) +
+                       (uint64_t)(wx * wx) * (uint64_t)((X - 1) * (X - 1));       // each term is below 2^12 * 2^32
+    return s < 0xFFFFFFFFull;
+}
+
 inline bool extents_fit(int64_t Z, int64_t Y, int64_t X, int pad) {
     constexpr int64_t limit = 1LL << 31;
     if (Z < 1 || Y < 1 || X < 1 || Z >= limit || Y >= limit || X >= limit) return false;

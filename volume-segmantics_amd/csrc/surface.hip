@@ -22,6 +22,11 @@
 //    the same search then reads global memory, from one buffer into another (that is what the workspace is for).
 //  No workgroup waits for another; every loop is bounded by an axis length.
 //
+// vs_edt_squared_scaled: the same three launches on a grid whose steps along z, y, x are the integers wz, wy, wx: the squared
+// distance is qz dz^2 + qy dy^2 + qx dx^2, q = w^2, still an integer.  The x pass writes qx m^2, the column passes search with
+// kk = q k^2 and keep the stop rule kk >= best, so a coarse axis ends its search after fewer steps.  The kernels are the same
+// templates; the unscaled instantiations never read the weight.
+//
 // vs_surface_distance_histogram: on a good prediction most surface voxels sit at d2 = 0, so bins 0..2 are counted in registers
 // and the next bins in an LDS histogram; a workgroup issues one 64-bit global atomic per non-zero small bin, and only the
 // far bins (rare, spread) go to global atomics one by one.
@@ -136,8 +141,9 @@ __global__ __launch_bounds__(kThreads) void surface_kernel(const uint8_t* __rest
 }
 
 // ---- distance transform ----------------------------------------------------------------------------------------------------------
-// in-row pass: one wave per row, lanes along x
-__global__ __launch_bounds__(kThreads) void edt_x_kernel(const uint8_t* __restrict__ seeds, int64_t rows, int X, uint32_t* d2) {
+// in-row pass: one wave per row, lanes along x.  kScaled: the squared step along x is q (vs_edt_squared_scaled), else 1.
+template <bool kScaled>
+__global__ __launch_bounds__(kThreads) void edt_x_kernel(const uint8_t* __restrict__ seeds, int64_t rows, int X, uint32_t* d2, uint32_t q) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     constexpr int kNone = 0x7fffffff;
     for (int64_t row = (int64_t)blockIdx.x * kWaves + wave; row < rows; row += (int64_t)gridDim.x * kWaves) {   // uniform over the wave
@@ -172,16 +178,19 @@ __global__ __launch_bounds__(kThreads) void edt_x_kernel(const uint8_t* __restri
                 const uint32_t dl = left == kInf ? kInf : (uint32_t)x - left;
                 const uint32_t dr = idx == kNone ? kInf : (uint32_t)(idx - x);
                 const uint32_t m = dl < dr ? dl : dr;
-                d[x] = m == kInf ? kInf : m * m;          // m <= 65535
+                if (kScaled) d[x] = m == kInf ? kInf : q * m * m;    // q m^2 <= q (X-1)^2 < 2^32 by the bound on the extents
+                else d[x] = m == kInf ? kInf : m * m;     // m <= 65535
             }
         }
     }
 }
 
 // column pass: address of (outer o, position p, column c) = (o * L + p) * inner + c.  y: outer = Z, L = Y, inner = X;
-// z: outer = 1, L = Z, inner = Y * X.  kLds: src may equal dst.
-template <bool kLds>
-__global__ __launch_bounds__(kAxisThreads) void edt_axis_kernel(const uint32_t* src, uint32_t* dst, int64_t inner, int L, int64_t tiles_per_outer) {
+// z: outer = 1, L = Z, inner = Y * X.  kLds: src may equal dst.  kScaled: the squared step along the axis is q, else 1; the stop
+// rule holds under a weight as it does without: no candidate at offset k can beat best once q k^2 >= best.
+template <bool kLds, bool kScaled>
+__global__ __launch_bounds__(kAxisThreads) void edt_axis_kernel(const uint32_t* src, uint32_t* dst, int64_t inner, int L, int64_t tiles_per_outer,
+                                                              uint32_t q) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tile[];      // [L][kTileCols] when kLds
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t outer = blockIdx.x / tiles_per_outer, t = blockIdx.x - outer * tiles_per_outer;
@@ -199,7 +208,8 @@ __global__ __launch_bounds__(kAxisThreads) void edt_axis_kernel(const uint32_t* 
         uint32_t best = kLds ? tile[p * kTileCols + lane] : s[(int64_t)p * inner];
         const int reach = p > L - 1 - p ? p : L - 1 - p;
         for (int k = 1; k <= reach; ++k) {               // k <= 65535: k * k fits
-            const uint32_t kk = (uint32_t)k * (uint32_t)k;
+            // scaled: q k^2 <= q (L-1)^2 < 2^32 by the bound on the extents
+            const uint32_t kk = kScaled ? q * (uint32_t)k * (uint32_t)k : (uint32_t)k * (uint32_t)k;
             if (kk >= best) break;
             if (p >= k) {
                 const uint32_t f = kLds ? tile[(p - k) * kTileCols + lane] : s[(int64_t)(p - k) * inner];
@@ -286,6 +296,47 @@ extern "C" size_t vs_edt_workspace_bytes(int64_t Z, int64_t Y, int64_t X) {
     return (global_y || global_z) ? (size_t)(Z * Y * X) * sizeof(uint32_t) : 0;
 }
 
+namespace {
+
+// the three passes of both entry points; q: the squared weights of z, y, x (read only when kScaled)
+template <bool kScaled>
+int edt_passes(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, const uint32_t q[3], uint32_t* d2, void* workspace, hipStream_t s) {
+    const int64_t rows = Z * Y;
+    const double volume = (double)(Z * Y * X);             // profile records (tools/surface_probe.py): x, then y, then z, in launch order
+    {
+        ProfScope prof(PK_POOL_MISC, 0.0, 5.0 * volume, s);          // seeds read, d2 written
+        int64_t grid = (rows + kWaves - 1) / kWaves;
+        if (grid > 4 * (int64_t)persistent_workgroups()) grid = 4 * (int64_t)persistent_workgroups();
+        hipLaunchKernelGGL(edt_x_kernel<kScaled>, dim3((unsigned)grid), dim3(kThreads), 0, s, seeds, rows, (int)X, d2, q[2]);
+        VS_LAUNCH_CHECK();
+    }
+    uint32_t* cur = d2;
+    uint32_t* other = (uint32_t*)workspace;
+    const struct { int64_t outer, inner; int L; uint32_t q; } passes[2] = {{Z, X, (int)Y, q[1]}, {1, Y * X, (int)Z, q[0]}};
+    for (const auto& p : passes) {
+        if (p.L == 1) continue;
+        const int64_t tiles = (p.inner + kTileCols - 1) / kTileCols;
+        VS_REQUIRE(p.outer * tiles < (1LL << 31), "edt_squared: volume too large");
+        const dim3 grid((unsigned)(p.outer * tiles));
+        ProfScope prof(PK_POOL_MISC, 0.0, 8.0 * volume, s);          // d2 read and written
+        if (p.L <= kMaxLdsAxis) {
+            const size_t lds = (size_t)p.L * kTileCols * sizeof(uint32_t);
+            if (lds > 64 * 1024)
+                VS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&edt_axis_kernel<true, kScaled>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 kMaxLdsAxis * kTileCols * (int)sizeof(uint32_t)));
+            hipLaunchKernelGGL((edt_axis_kernel<true, kScaled>), grid, dim3(kAxisThreads), lds, s, cur, cur, p.inner, p.L, tiles, p.q);
+        } else {
+            hipLaunchKernelGGL((edt_axis_kernel<false, kScaled>), grid, dim3(kAxisThreads), 0, s, cur, other, p.inner, p.L, tiles, p.q);
+            uint32_t* t = cur; cur = other; other = t;
+        }
+        VS_LAUNCH_CHECK();
+    }
+    if (cur != d2) VS_CHECK_HIP(hipMemcpyAsync(d2, cur, (size_t)(Z * Y * X) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    return VS_OK;
+}
+
+}  // namespace
+
 extern "C" int vs_edt_squared(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, uint32_t* d2, void* workspace, size_t workspace_bytes,
                               void* stream) {
     VS_REQUIRE(extents_fit(Z, Y, X),
@@ -296,39 +347,23 @@ extern "C" int vs_edt_squared(const uint8_t* seeds, int64_t Z, int64_t Y, int64_
     const size_t need = vs_edt_workspace_bytes(Z, Y, X);
     VS_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "edt_squared: workspace of %zu bytes, %zu needed (vs_edt_workspace_bytes)",
                workspace_bytes, need);
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t rows = Z * Y;
-    const double volume = (double)(Z * Y * X);             // profile records (tools/surface_probe.py): x, then y, then z, in launch order
-    {
-        ProfScope prof(PK_POOL_MISC, 0.0, 5.0 * volume, s);          // seeds read, d2 written
-        int64_t grid = (rows + kWaves - 1) / kWaves;
-        if (grid > 4 * (int64_t)persistent_workgroups()) grid = 4 * (int64_t)persistent_workgroups();
-        hipLaunchKernelGGL(edt_x_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, seeds, rows, (int)X, d2);
-        VS_LAUNCH_CHECK();
-    }
-    uint32_t* cur = d2;
-    uint32_t* other = (uint32_t*)workspace;
-    const struct { int64_t outer, inner; int L; } passes[2] = {{Z, X, (int)Y}, {1, Y * X, (int)Z}};
-    for (const auto& p : passes) {
-        if (p.L == 1) continue;
-        const int64_t tiles = (p.inner + kTileCols - 1) / kTileCols;
-        VS_REQUIRE(p.outer * tiles < (1LL << 31), "edt_squared: volume too large");
-        const dim3 grid((unsigned)(p.outer * tiles));
-        ProfScope prof(PK_POOL_MISC, 0.0, 8.0 * volume, s);          // d2 read and written
-        if (p.L <= kMaxLdsAxis) {
-            const size_t lds = (size_t)p.L * kTileCols * sizeof(uint32_t);
-            if (lds > 64 * 1024)
-                VS_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&edt_axis_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 kMaxLdsAxis * kTileCols * (int)sizeof(uint32_t)));
-            hipLaunchKernelGGL(edt_axis_kernel<true>, grid, dim3(kAxisThreads), lds, s, cur, cur, p.inner, p.L, tiles);
-        } else {
-            hipLaunchKernelGGL(edt_axis_kernel<false>, grid, dim3(kAxisThreads), 0, s, cur, other, p.inner, p.L, tiles);
-            uint32_t* t = cur; cur = other; other = t;
-        }
-        VS_LAUNCH_CHECK();
-    }
-    if (cur != d2) VS_CHECK_HIP(hipMemcpyAsync(d2, cur, (size_t)(Z * Y * X) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    return VS_OK;
+    const uint32_t q[3] = {1u, 1u, 1u};
+    return edt_passes<false>(seeds, Z, Y, X, q, d2, workspace, (hipStream_t)stream);
+}
+
+extern "C" int vs_edt_squared_scaled(const uint8_t* seeds, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, uint32_t* d2, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    VS_REQUIRE(weighted_distances_fit(Z, Y, X, wz, wy, wx),
+               "edt_squared_scaled: extents %lld x %lld x %lld under weights %d, %d, %d - every weight must be 1..64 and wz^2 (Z-1)^2 + wy^2 (Y-1)^2 + "
+               "wx^2 (X-1)^2 below 2^32 - 1 for squared distances to fit a uint32",
+               (long long)Z, (long long)Y, (long long)X, wz, wy, wx);
+    VS_REQUIRE(seeds && d2, "edt_squared_scaled: null volume");
+    VS_REQUIRE((uintptr_t)d2 % 4 == 0 && (uintptr_t)workspace % 4 == 0, "edt_squared_scaled: d2 and workspace must be 4-byte aligned");
+    const size_t need = vs_edt_workspace_bytes(Z, Y, X);       // the weighted bound is the tighter one: the extents fit here too
+    VS_REQUIRE(workspace_bytes >= need && (need == 0 || workspace), "edt_squared_scaled: workspace of %zu bytes, %zu needed (vs_edt_workspace_bytes)",
+               workspace_bytes, need);
+    const uint32_t q[3] = {(uint32_t)(wz * wz), (uint32_t)(wy * wy), (uint32_t)(wx * wx)};
+    return edt_passes<true>(seeds, Z, Y, X, q, d2, workspace, (hipStream_t)stream);
 }
 
 extern "C" int vs_surface_distance_histogram(const uint8_t* from_surface, const uint32_t* d2, int64_t n, int64_t bins, int64_t* hist,

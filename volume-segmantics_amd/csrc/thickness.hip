@@ -52,20 +52,32 @@ bool thickness_extents_fit(int64_t Z, int64_t Y, int64_t X) {
     return s < 0xFFFFFFFFull;
 }
 
-// levels of the sparse table: bit_length(min(2 h + 1, X)), h the half width of the widest span of a ball of squared radius max_r
-int table_levels(int64_t X, uint32_t max_r) {
-    int64_t longest = 2 * (int64_t)isqrt_u32(max_r - 1) + 1;
+// the squared steps of the grid along z, y, x: q = w^2, w the integer weights of the _scaled entry points; 1, 1, 1 otherwise
+struct Steps { uint32_t qz, qy, qx; };
+constexpr Steps kUnit = {1u, 1u, 1u};
+
+// fewer than 2^31 voxels, weights 1..64, and the extents vs_edt_squared_scaled takes
+bool scaled_extents_fit(int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx) {
+    return thickness_extents_fit(Z, Y, X) && weighted_distances_fit(Z, Y, X, wz, wy, wx);
+}
+
+Steps steps_of(int wz, int wy, int wx) { return Steps{(uint32_t)(wz * wz), (uint32_t)(wy * wy), (uint32_t)(wx * wx)}; }
+
+// levels of the sparse table: bit_length(min(2 h + 1, X)), h the half width of the widest span of a ball of squared radius max_r:
+// the largest h with qx h^2 < max_r
+int table_levels(int64_t X, uint32_t max_r, uint32_t qx = 1u) {
+    int64_t longest = 2 * (int64_t)isqrt_u32((max_r - 1) / qx) + 1;
     if (longest > X) longest = X;
     int k = 0;
     while (longest) { ++k; longest >>= 1; }
     return k;
 }
 
-// rows (dz, dy) of the bounding square of a ball of half width h around (z, y), clipped to the volume
-__device__ __forceinline__ void ball_rows(int z, int y, int h, int Z, int Y, int& z0, int& y0, int& nz, int& ny) {
-    z0 = z - h > 0 ? z - h : 0;
-    y0 = y - h > 0 ? y - h : 0;
-    const int z1 = (int64_t)z + h < Z - 1 ? z + h : Z - 1, y1 = (int64_t)y + h < Y - 1 ? y + h : Y - 1;
+// rows (dz, dy) of the bounding rectangle of a ball that reaches hz planes and hy lines from (z, y), clipped to the volume
+__device__ __forceinline__ void ball_rows(int z, int y, int hz, int hy, int Z, int Y, int& z0, int& y0, int& nz, int& ny) {
+    z0 = z - hz > 0 ? z - hz : 0;
+    y0 = y - hy > 0 ? y - hy : 0;
+    const int z1 = (int64_t)z + hz < Z - 1 ? z + hz : Z - 1, y1 = (int64_t)y + hy < Y - 1 ? y + hy : Y - 1;
     nz = z1 - z0 + 1;
     ny = y1 - y0 + 1;
 }
@@ -77,16 +89,20 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 }
 
 // ---- centres ---------------------------------------------------------------------------------------------------------------------
-// whether voxel i is a centre; the rows its ball will paint are added to spans
+// whether voxel i is a centre; the rows its ball will paint are added to spans.  kScaled: need has 7 rows, one per non-empty set
+// of axes on which the neighbour's offset is non-zero (row 4 [z] + 2 [y] + [x] - 1), and the ball reaches isqrt((R - 1) / q) rows.
+template <bool kScaled>
 __device__ __forceinline__ bool is_centre(const uint32_t* __restrict__ r, int64_t i, int Z, int Y, int X, int64_t n, int64_t plane,
-                                          const uint32_t* __restrict__ need, uint32_t need_len, unsigned long long& spans) {
+                                          const uint32_t* __restrict__ need, uint32_t need_len, Steps q, unsigned long long& spans) {
     const uint32_t rv = i < n ? r[i] : 0u;
     if (rv == 0u || rv == kInf) return false;
     const int64_t line = i / X;
     const int x = (int)(i - line * X), z = (int)(line / Y);
     const int y = (int)(line - (int64_t)z * Y);
     if (rv < need_len) {
-        const uint32_t thr[3] = {need[rv], need[(size_t)need_len + rv], need[2 * (size_t)need_len + rv]};
+        uint32_t thr[kScaled ? 7 : 3];
+#pragma unroll
+        for (int j = 0; j < (kScaled ? 7 : 3); ++j) thr[j] = need[j * (size_t)need_len + rv];
         bool keep = true;
 #pragma unroll
         for (int dz = -1; dz <= 1; ++dz) {
@@ -94,7 +110,8 @@ __device__ __forceinline__ bool is_centre(const uint32_t* __restrict__ r, int64_
             for (int dy = -1; dy <= 1; ++dy) {
 #pragma unroll
                 for (int dx = -1; dx <= 1; ++dx) {
-                    const int cls = (dz != 0) + (dy != 0) + (dx != 0);       // 1 = across a face, 2 = an edge, 3 = a corner
+                    // unscaled: 1 = across a face, 2 = an edge, 3 = a corner; scaled: the set of axes the offset moves along
+                    const int cls = kScaled ? 4 * (dz != 0) + 2 * (dy != 0) + (dx != 0) : (dz != 0) + (dy != 0) + (dx != 0);
                     if (cls == 0) continue;
                     const int zz = z + dz, yy = y + dy, xx = x + dx;
                     if (zz < 0 || zz >= Z || yy < 0 || yy >= Y || xx < 0 || xx >= X) continue;
@@ -105,17 +122,19 @@ __device__ __forceinline__ bool is_centre(const uint32_t* __restrict__ r, int64_
         if (!keep) return false;
     }
     int z0, y0, nz, ny;
-    ball_rows(z, y, (int)isqrt_u32(rv - 1u), Z, Y, z0, y0, nz, ny);
+    if (kScaled) ball_rows(z, y, (int)isqrt_u32((rv - 1u) / q.qz), (int)isqrt_u32((rv - 1u) / q.qy), Z, Y, z0, y0, nz, ny);
+    else { const int h = (int)isqrt_u32(rv - 1u); ball_rows(z, y, h, h, Z, Y, z0, y0, nz, ny); }
     spans += (unsigned long long)nz * (unsigned long long)ny;
     return true;
 }
 
 // A workgroup looks at kItems x kThreads consecutive voxels per step and takes its place in the list with ONE 64-bit add: returning
 // atomics on one address queue up whoever issues them, and one per wave of 64 voxels was most of this sweep's time.
+template <bool kScaled>
 __global__ __launch_bounds__(kThreads) void thickness_centres_kernel(const uint32_t* __restrict__ r, int Z, int Y, int X, int64_t n,
                                                                    const uint32_t* __restrict__ need, uint32_t need_len,
                                                                    int32_t* __restrict__ centres, int64_t capacity,
-                                                                   unsigned long long* __restrict__ totals) {
+                                                                   unsigned long long* __restrict__ totals, Steps q) {
     __shared__ unsigned long long wave_first[kWaves];          // in: the wave's count; out: the wave's first place
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t plane = (int64_t)Y * X, step = (int64_t)kItems * kThreads;
@@ -125,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void thickness_centres_kernel(const uint3
         int mine = 0;
 #pragma unroll
         for (int u = 0; u < kItems; ++u) {
-            mask[u] = __ballot(is_centre(r, base + u * kThreads + threadIdx.x, Z, Y, X, n, plane, need, need_len, spans));
+            mask[u] = __ballot(is_centre<kScaled>(r, base + u * kThreads + threadIdx.x, Z, Y, X, n, plane, need, need_len, q, spans));
             mine += __popcll(mask[u]);
         }
         if (lane == 0) wave_first[wave] = (unsigned long long)mine;
@@ -159,9 +178,11 @@ __global__ __launch_bounds__(kThreads) void thickness_centres_kernel(const uint3
 }
 
 // ---- painting --------------------------------------------------------------------------------------------------------------------
+// kScaled: row (dz, dy) lies qz dz^2 + qy dy^2 off the centre and its half width is the largest h with qx h^2 < m
+template <bool kScaled>
 __global__ __launch_bounds__(kThreads) void thickness_paint_kernel(const uint32_t* __restrict__ r, int Z, int Y, int X, int64_t n,
                                                                  const int32_t* __restrict__ centres, int64_t count, uint32_t* levels,
-                                                                 int K) {
+                                                                 int K, Steps q) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // every wave of the workgroup holds the same 64 centres, one per lane
     const int64_t c = (int64_t)blockIdx.x * kBatch + lane;
@@ -186,14 +207,18 @@ __global__ __launch_bounds__(kThreads) void thickness_paint_kernel(const uint32_
         largest = u > largest ? u : largest;
     }
     if (reach < 0) return;
-    const int hz = reach < Z - 1 ? reach : Z - 1, hy = reach < Y - 1 ? reach : Y - 1;      // no row further than the volume is long
+    // the rows of the batch's widest ball; no row further than the volume is long
+    const int rz = kScaled ? (int)isqrt_u32((largest - 1u) / q.qz) : reach, ry = kScaled ? (int)isqrt_u32((largest - 1u) / q.qy) : reach;
+    const int hz = rz < Z - 1 ? rz : Z - 1, hy = ry < Y - 1 ? ry : Y - 1;
     for (int dz = -hz + (int)blockIdx.y; dz <= hz; dz += (int)gridDim.y) {                  // uniform over the workgroup
         for (int dy = -hy + wave; dy <= hy; dy += kWaves) {                                 // uniform over the wave
-            const uint64_t off2 = (uint64_t)((int64_t)dz * dz + (int64_t)dy * dy);
+            const uint64_t off2 = kScaled ? (uint64_t)q.qz * (uint64_t)((int64_t)dz * dz) + (uint64_t)q.qy * (uint64_t)((int64_t)dy * dy)
+                                          : (uint64_t)((int64_t)dz * dz + (int64_t)dy * dy);
             if (off2 >= largest) continue;            // outside the batch's widest ball
             const int zz = z + dz, yy = y + dy;
             if (off2 >= rv || zz < 0 || zz >= Z || yy < 0 || yy >= Y) continue;          // m = R - dz^2 - dy^2 < 1, or no such row
-            const int hs = (int)isqrt_u32(rv - (uint32_t)off2 - 1u);                      // the largest h with h^2 < m
+            // the largest h with h^2 < m; scaled: with qx h^2 < m, isqrt((m - 1) / qx)
+            const int hs = (int)isqrt_u32(kScaled ? (rv - (uint32_t)off2 - 1u) / q.qx : rv - (uint32_t)off2 - 1u);
             const int first = x - hs > 0 ? x - hs : 0, last = x + hs < X - 1 ? x + hs : X - 1;
             const int k = 31 - __clz(last - first + 1);
             if (k >= K) continue;                     // cannot happen while max_r bounds every R: no store outside the table
@@ -231,15 +256,15 @@ int sweep_grid(int64_t n) {
     return (int)(grid < 1 ? 1 : grid);
 }
 
-}  // namespace
-
-extern "C" size_t vs_thickness_workspace_bytes(int64_t Z, int64_t Y, int64_t X, int64_t max_r) {
+// ---- the entry points, unscaled and scaled: one body each -------------------------------------------------------------------------
+size_t workspace_bytes_of(int64_t Z, int64_t Y, int64_t X, int64_t max_r, Steps q) {
     if (!thickness_extents_fit(Z, Y, X) || max_r < 1 || max_r >= (int64_t)kInf) return 0;
-    return (size_t)table_levels(X, (uint32_t)max_r) * (size_t)(Z * Y * X) * sizeof(uint32_t);
+    return (size_t)table_levels(X, (uint32_t)max_r, q.qx) * (size_t)(Z * Y * X) * sizeof(uint32_t);
 }
 
-extern "C" int vs_thickness_centres(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const uint32_t* need, int64_t need_len,
-                                    int32_t* centres, int64_t capacity, int64_t* totals, void* stream) {
+template <bool kScaled>
+int centres_impl(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const uint32_t* need, int64_t need_len, int32_t* centres, int64_t capacity,
+                 int64_t* totals, Steps q, void* stream) {
     VS_REQUIRE(thickness_extents_fit(Z, Y, X),
                "thickness_centres: extents %lld x %lld x %lld - fewer than 2^31 voxels and (Z-1)^2 + (Y-1)^2 + (X-1)^2 below 2^32 - 1",
                (long long)Z, (long long)Y, (long long)X);
@@ -252,14 +277,15 @@ extern "C" int vs_thickness_centres(const uint32_t* r, int64_t Z, int64_t Y, int
     hipStream_t s = (hipStream_t)stream;
     VS_CHECK_HIP(hipMemsetAsync(totals, 0, 2 * sizeof(int64_t), s));
     const int64_t n = Z * Y * X;
-    hipLaunchKernelGGL(thickness_centres_kernel, dim3((unsigned)sweep_grid((n + kItems - 1) / kItems)), dim3(kThreads), 0, s, r, (int)Z, (int)Y, (int)X, n, need,
-                       (uint32_t)need_len, centres, capacity, (unsigned long long*)totals);
+    hipLaunchKernelGGL(thickness_centres_kernel<kScaled>, dim3((unsigned)sweep_grid((n + kItems - 1) / kItems)), dim3(kThreads), 0, s, r, (int)Z, (int)Y, (int)X,
+                       n, need, (uint32_t)need_len, centres, capacity, (unsigned long long*)totals, q);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
 
-extern "C" int vs_thickness_paint(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const int32_t* centres, int64_t count, int64_t largest_r,
-                                  int64_t max_r, void* workspace, size_t workspace_bytes, int zero_first, void* stream) {
+template <bool kScaled>
+int paint_impl(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const int32_t* centres, int64_t count, int64_t largest_r, int64_t max_r,
+               void* workspace, size_t workspace_bytes, int zero_first, Steps q, void* stream) {
     VS_REQUIRE(thickness_extents_fit(Z, Y, X),
                "thickness_paint: extents %lld x %lld x %lld - fewer than 2^31 voxels and (Z-1)^2 + (Y-1)^2 + (X-1)^2 below 2^32 - 1",
                (long long)Z, (long long)Y, (long long)X);
@@ -269,7 +295,7 @@ extern "C" int vs_thickness_paint(const uint32_t* r, int64_t Z, int64_t Y, int64
     const int64_t n = Z * Y * X;
     VS_REQUIRE(count >= 0 && count <= n, "thickness_paint: %lld centres in a volume of %lld voxels", (long long)count, (long long)n);
     VS_REQUIRE(r && workspace && (centres || count == 0), "thickness_paint: null argument");
-    const size_t need_bytes = vs_thickness_workspace_bytes(Z, Y, X, max_r);
+    const size_t need_bytes = workspace_bytes_of(Z, Y, X, max_r, q);
     VS_REQUIRE(workspace_bytes >= need_bytes, "thickness_paint: workspace of %zu bytes, %zu needed (vs_thickness_workspace_bytes)", workspace_bytes,
                need_bytes);
     VS_REQUIRE((uintptr_t)r % 4 == 0 && (uintptr_t)centres % 4 == 0 && (uintptr_t)workspace % 4 == 0,
@@ -278,34 +304,34 @@ extern "C" int vs_thickness_paint(const uint32_t* r, int64_t Z, int64_t Y, int64
     if (zero_first) VS_CHECK_HIP(hipMemsetAsync(workspace, 0, need_bytes, s));
     if (count == 0) return VS_OK;
     // the rows of the call's largest ball decide how many workgroups share a batch: each takes every gridDim.y-th plane dz
-    const int64_t reach = (int64_t)isqrt_u32((uint32_t)largest_r - 1u);
-    const int64_t planes = 2 * (reach < Z - 1 ? reach : Z - 1) + 1, lines = 2 * (reach < Y - 1 ? reach : Y - 1) + 1;
+    const int64_t rz = (int64_t)isqrt_u32(((uint32_t)largest_r - 1u) / q.qz), ry = (int64_t)isqrt_u32(((uint32_t)largest_r - 1u) / q.qy);
+    const int64_t planes = 2 * (rz < Z - 1 ? rz : Z - 1) + 1, lines = 2 * (ry < Y - 1 ? ry : Y - 1) + 1;
     int64_t slices = (planes * lines + (int64_t)kWaves * kWaveRows - 1) / ((int64_t)kWaves * kWaveRows);
     if (slices < 1) slices = 1;
     if (slices > planes) slices = planes;
     if (slices > kMaxSlices) slices = kMaxSlices;
     const int64_t batches = (count + kBatch - 1) / kBatch;
-    hipLaunchKernelGGL(thickness_paint_kernel, dim3((unsigned)batches, (unsigned)slices), dim3(kThreads), 0, s, r, (int)Z, (int)Y, (int)X, n, centres,
-                       count, (uint32_t*)workspace, table_levels(X, (uint32_t)max_r));
+    hipLaunchKernelGGL(thickness_paint_kernel<kScaled>, dim3((unsigned)batches, (unsigned)slices), dim3(kThreads), 0, s, r, (int)Z, (int)Y, (int)X, n,
+                       centres, count, (uint32_t*)workspace, table_levels(X, (uint32_t)max_r, q.qx), q);
     VS_LAUNCH_CHECK();
     return VS_OK;
 }
 
-extern "C" int vs_thickness_resolve(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int64_t max_r, void* workspace,
-                                    size_t workspace_bytes, uint32_t* t2, void* stream) {
+int resolve_impl(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int64_t max_r, void* workspace, size_t workspace_bytes,
+                 uint32_t* t2, Steps q, void* stream) {
     VS_REQUIRE(thickness_extents_fit(Z, Y, X),
                "thickness_resolve: extents %lld x %lld x %lld - fewer than 2^31 voxels and (Z-1)^2 + (Y-1)^2 + (X-1)^2 below 2^32 - 1",
                (long long)Z, (long long)Y, (long long)X);
     VS_REQUIRE(value >= 0 && value <= 255, "thickness_resolve: value %d is not a uint8 value", value);
     VS_REQUIRE(max_r >= 1 && max_r < (int64_t)kInf, "thickness_resolve: squared radius %lld - 1 <= max_r < 2^32 - 1", (long long)max_r);
     VS_REQUIRE(labels && workspace && t2, "thickness_resolve: null argument");
-    const size_t need_bytes = vs_thickness_workspace_bytes(Z, Y, X, max_r);
+    const size_t need_bytes = workspace_bytes_of(Z, Y, X, max_r, q);
     VS_REQUIRE(workspace_bytes >= need_bytes, "thickness_resolve: workspace of %zu bytes, %zu needed (vs_thickness_workspace_bytes)", workspace_bytes,
                need_bytes);
     VS_REQUIRE((uintptr_t)workspace % 4 == 0 && (uintptr_t)t2 % 4 == 0, "thickness_resolve: workspace and t2 must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const int64_t n = Z * Y * X;
-    const int K = table_levels(X, (uint32_t)max_r);
+    const int K = table_levels(X, (uint32_t)max_r, q.qx);
     uint32_t* levels = (uint32_t*)workspace;
     const dim3 grid((unsigned)sweep_grid(n));
     if (K == 1) {
@@ -318,4 +344,52 @@ extern "C" int vs_thickness_resolve(const uint8_t* labels, int64_t Z, int64_t Y,
         VS_LAUNCH_CHECK();
     }
     return VS_OK;
+}
+
+}  // namespace
+
+#define VS_REQUIRE_WEIGHTS(what)                                                                                                              \
+    VS_REQUIRE(scaled_extents_fit(Z, Y, X, wz, wy, wx),                                                                                        \
+               what ": extents %lld x %lld x %lld under weights %d, %d, %d - fewer than 2^31 voxels, every weight 1..64 and wz^2 (Z-1)^2 + "  \
+                    "wy^2 (Y-1)^2 + wx^2 (X-1)^2 below 2^32 - 1",                                                                             \
+               (long long)Z, (long long)Y, (long long)X, wz, wy, wx)
+
+extern "C" size_t vs_thickness_workspace_bytes(int64_t Z, int64_t Y, int64_t X, int64_t max_r) { return workspace_bytes_of(Z, Y, X, max_r, kUnit); }
+
+extern "C" size_t vs_thickness_workspace_bytes_scaled(int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, int64_t max_r) {
+    return scaled_extents_fit(Z, Y, X, wz, wy, wx) ? workspace_bytes_of(Z, Y, X, max_r, steps_of(wz, wy, wx)) : 0;
+}
+
+extern "C" int vs_thickness_centres(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const uint32_t* need, int64_t need_len,
+                                    int32_t* centres, int64_t capacity, int64_t* totals, void* stream) {
+    return centres_impl<false>(r, Z, Y, X, need, need_len, centres, capacity, totals, kUnit, stream);
+}
+
+extern "C" int vs_thickness_centres_scaled(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, const uint32_t* need,
+                                           int64_t need_len, int32_t* centres, int64_t capacity, int64_t* totals, void* stream) {
+    VS_REQUIRE_WEIGHTS("thickness_centres_scaled");
+    return centres_impl<true>(r, Z, Y, X, need, need_len, centres, capacity, totals, steps_of(wz, wy, wx), stream);
+}
+
+extern "C" int vs_thickness_paint(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, const int32_t* centres, int64_t count, int64_t largest_r,
+                                  int64_t max_r, void* workspace, size_t workspace_bytes, int zero_first, void* stream) {
+    return paint_impl<false>(r, Z, Y, X, centres, count, largest_r, max_r, workspace, workspace_bytes, zero_first, kUnit, stream);
+}
+
+extern "C" int vs_thickness_paint_scaled(const uint32_t* r, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, const int32_t* centres,
+                                         int64_t count, int64_t largest_r, int64_t max_r, void* workspace, size_t workspace_bytes, int zero_first,
+                                         void* stream) {
+    VS_REQUIRE_WEIGHTS("thickness_paint_scaled");
+    return paint_impl<true>(r, Z, Y, X, centres, count, largest_r, max_r, workspace, workspace_bytes, zero_first, steps_of(wz, wy, wx), stream);
+}
+
+extern "C" int vs_thickness_resolve(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int value, int64_t max_r, void* workspace,
+                                    size_t workspace_bytes, uint32_t* t2, void* stream) {
+    return resolve_impl(labels, Z, Y, X, value, max_r, workspace, workspace_bytes, t2, kUnit, stream);
+}
+
+extern "C" int vs_thickness_resolve_scaled(const uint8_t* labels, int64_t Z, int64_t Y, int64_t X, int wz, int wy, int wx, int value, int64_t max_r,
+                                           void* workspace, size_t workspace_bytes, uint32_t* t2, void* stream) {
+    VS_REQUIRE_WEIGHTS("thickness_resolve_scaled");
+    return resolve_impl(labels, Z, Y, X, value, max_r, workspace, workspace_bytes, t2, steps_of(wz, wy, wx), stream);
 }

@@ -98,7 +98,10 @@ class VolSeg2DPredictionManager(BaseDataManager):
         diameter of the largest ball inside the material that contains the voxel, physical units from ``thickness_voxel_size``, the
         work bounded by ``thickness_max_work``): the per-value figures are logged, ``last_thickness`` keeps the squared map, the histograms
         and the figures, and ``<stem>_thickness.json`` / ``.csv`` - with ``thickness_save_volume`` also ``<stem>_thickness.h5``, the float32
-        thicknesses - are written beside the label volume."""
+        thicknesses - are written beside the label volume.
+        ``voxel_spacing: [sz, sy, sx]`` states the grid for all of them (utilities/label_volume.py ``voxel_grid``): the default of
+        ``measure_voxel_size`` and ``mesh_voxel_size``, the weighted distance map of ``measure_separate`` and of the thickness, whose
+        files then carry ``voxel_spacing``, ``weights`` and ``unit``; it is an error beside ``thickness_voxel_size``."""
         one_hot = self.settings.one_hot
         steps = [step for step in LABEL_STEPS if step.asked(self.settings)]
         if one_hot and steps:
@@ -160,7 +163,7 @@ class VolSeg2DPredictionManager(BaseDataManager):
         label codes where they record the values (evaluation.truth_label_values); ``evaluation_ignore_label`` sets voxels aside.
         Returns the scores; ``last_evaluation`` keeps the prediction, the dropped counts and the per-slice Dice.  With the settings key
         ``evaluation_surface_distances: true`` the surface distances (utilities/surface_distance.py: Hausdorff, its 95th percentile,
-        average symmetric surface distance, surface Dice at ``evaluation_surface_tolerance``, distances in ``evaluation_voxel_size``) are
+        average symmetric surface distance, surface Dice at ``evaluation_surface_tolerance``, distances in ``evaluation_voxel_size``, or exact on the anisotropic grid of ``voxel_spacing``) are
         computed as well, logged, written to ``<stem>_surface_scores.csv`` / ``.json`` and kept in ``last_evaluation["surface_scores"]``.
         With ``evaluation_object_scores: true`` the object-level scores (utilities/object_scores.py: true and predicted connected
         components under ``evaluation_object_connectivity`` matched at ``evaluation_object_iou``; precision, recall, F1, panoptic quality,

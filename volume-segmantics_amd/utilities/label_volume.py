@@ -145,6 +145,67 @@ def voxel_size(voxel_size) -> tuple[float, float, float]:
     return float(size[0]), float(size[1]), float(size[2])
 
 
+MAX_WEIGHT = 64               # the largest integer weight of an axis (csrc/surface.hip: vs_edt_squared_scaled)
+UNIT_WEIGHTS = (1, 1, 1)
+
+
+def voxel_grid(spacing) -> tuple[tuple[int, int, int], float]:
+    """``(weights (wz, wy, wx), unit u)`` of ``voxel_spacing: [sz, sy, sx]``: positive integers with gcd 1, each at most 64, with ``s_i =
+    w_i u``.  The weight of the smallest step is the first ``m`` in 1..64 for which every ``s_i / s_min * m`` lies within 1e-6 relative of
+    an integer at most 64, and ``u = s_min / m``.  With ``q_i = w_i^2`` the squared distance between two voxels is the integer ``D = qz dz^2
+    + qy dy^2 + qx dx^2`` and a physical distance is ``u sqrt(D)``.  Steps in no such ratio are refused."""
+    try:
+        size = np.asarray(spacing, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        size = np.zeros(0)
+    if size.size != 3 or not np.all(np.isfinite(size)) or not np.all(size > 0):
+        raise ValueError(f"voxel_spacing {spacing!r}: it is three finite positive numbers, [sz, sy, sx]")
+    smallest = float(size.min())
+    for m in range(1, MAX_WEIGHT + 1):
+        scaled = size / smallest * m
+        w = np.rint(scaled)
+        if np.all(np.abs(scaled - w) <= 1e-6 * scaled) and np.all(w >= 1) and np.all(w <= MAX_WEIGHT):
+            return (int(w[0]), int(w[1]), int(w[2])), smallest / m         # the first such m leaves no common factor
+    raise ValueError(f"voxel_spacing {spacing!r}: the steps must be in a ratio of integers of at most {MAX_WEIGHT} for distances to stay exact "
+                     f"integers - round the steps, for example to two significant digits")
+
+
+def check_weights(weights, zyx) -> tuple[int, int, int]:
+    """the integer weights of the axes as a tuple, after checking that every weighted squared distance of a ``zyx`` volume fits below
+    2^32 - 1; an axis of length 1 contributes nothing"""
+    w = tuple(int(x) for x in weights)
+    if len(w) != 3 or any(not 1 <= x <= MAX_WEIGHT for x in w):
+        raise ValueError(f"weights {weights!r}: three integers of 1..{MAX_WEIGHT}")
+    most = sum(x * x * (e - 1) ** 2 for x, e in zip(w, zyx))
+    if most >= 0xFFFFFFFF:
+        raise ValueError(f"a volume of shape {tuple(zyx)} under the weights {w} can hold a squared distance of {most}: wz^2 (Z-1)^2 + wy^2 (Y-1)^2 + "
+                         f"wx^2 (X-1)^2 must be below 2^32 - 1 = 4294967295")
+    return w
+
+
+def grid_of(spacing, zyx) -> tuple[tuple[int, int, int], float]:
+    """``voxel_grid`` for a ``spacing=`` argument: None is the unit grid; the weights are checked against the volume"""
+    if spacing is None:
+        return UNIT_WEIGHTS, 1.0
+    weights, unit = voxel_grid(spacing)
+    return check_weights(weights, zyx), unit
+
+
+def spacing_settings(settings, *scalar_keys):
+    """the optional predict-settings key ``voxel_spacing`` as ``(spacing [sz, sy, sx] as floats, weights, unit)``, or None where the key is
+    absent.  ``scalar_keys``: the per-analysis keys that hold ONE voxel size - setting one of them beside ``voxel_spacing`` is an error,
+    for a scalar cannot override a grid."""
+    spacing = getattr(settings, "voxel_spacing", None)
+    if spacing is None:
+        return None
+    weights, unit = voxel_grid(spacing)
+    for key in scalar_keys:
+        if getattr(settings, key, None) is not None:
+            raise ValueError(f"voxel_spacing and {key} are both set: {key} is one number and cannot override the grid of voxel_spacing - "
+                             f"remove one of the two keys")
+    return [float(s) for s in np.asarray(spacing, dtype=np.float64).reshape(-1)], weights, unit
+
+
 def json_number(x):
     """a float for a JSON document: NaN is written as null, infinity as the string "inf" """
     x = float(x)

@@ -105,7 +105,8 @@ def _measure_host(vol: np.ndarray, connectivity: int, min_voxels: int, backgroun
         comp = co.label_components(vol, connectivity, device="cpu")
     else:
         from . import separation as sp
-        comp, report, contacts = sp.separate_prepared(vol, vol.shape, None, separate["values"], connectivity, separate["depth"], separate["max_pairs"])
+        comp, report, contacts = sp.separate_prepared(vol, vol.shape, None, separate["values"], connectivity, separate["depth"], separate["max_pairs"],
+                                                             separate.get("weights", lv.UNIT_WEIGHTS))
         separation = dict(report=report, contacts=contacts)
     flat_c = comp.reshape(-1)
     size = np.bincount(flat_c, minlength=flat_c.size)
@@ -153,7 +154,8 @@ def _measure_device(v, zyx, device, connectivity: int, min_voxels: int, backgrou
         comp = co.label_device(v, zyx, connectivity)
     else:
         from . import separation as sp
-        comp, report, contacts = sp.separate_prepared(v, zyx, device, separate["values"], connectivity, separate["depth"], separate["max_pairs"])
+        comp, report, contacts = sp.separate_prepared(v, zyx, device, separate["values"], connectivity, separate["depth"], separate["max_pairs"],
+                                                             separate.get("weights", lv.UNIT_WEIGHTS))
         separation = dict(report=report, contacts=contacts)
     size, _ = co.sizes_device(comp, zyx)
     roots = torch.nonzero(size).reshape(-1)                           # ascending
@@ -289,8 +291,8 @@ def object_table(raw: dict, voxel_size=1.0, shape=None) -> dict:
 # ---- settings and reporting ------------------------------------------------------------------------------------------------------
 def measurement_settings(settings) -> dict:
     """the optional predict-settings keys ``measure_objects``, ``measure_connectivity`` (default: ``postprocess_connectivity`` where that
-    is set, else 6), ``measure_min_voxels``, ``measure_background``, ``measure_voxel_size`` and ``measure_save_ids`` as arguments, with
-    ``active``: whether ``measure_objects`` asks for work"""
+    is set, else 6), ``measure_min_voxels``, ``measure_background``, ``measure_voxel_size`` (default: ``voxel_spacing`` where that is set, else
+    1.0) and ``measure_save_ids`` as arguments, with ``active``: whether ``measure_objects`` asks for work"""
     connectivity = getattr(settings, "measure_connectivity", None) or getattr(settings, "postprocess_connectivity", None) or 6
     connectivity = int(connectivity)
     if connectivity not in (6, 18, 26):
@@ -300,6 +302,9 @@ def measurement_settings(settings) -> dict:
     if min_voxels < 1:
         raise ValueError("measure_min_voxels must be at least 1")
     voxel_size = getattr(settings, "measure_voxel_size", None)
+    grid = lv.spacing_settings(settings)
+    if voxel_size is None and grid is not None:
+        voxel_size = grid[0]
     return dict(active=bool(getattr(settings, "measure_objects", False)), connectivity=connectivity, min_voxels=min_voxels,
                 include_background=bool(getattr(settings, "measure_background", False)),
                 voxel_size=list(lv.voxel_size(1.0 if voxel_size is None else voxel_size)), save_ids=bool(getattr(settings, "measure_save_ids", False)))
@@ -317,7 +322,7 @@ def measure_label_volume(vol, settings, device=None) -> dict:
         raw, ids, _ = _measure(vol, m["connectivity"], m["min_voxels"], 0, m["include_background"], device, m["save_ids"])
         return {"settings": m, "raw": raw, "table": object_table(raw, m["voxel_size"]), "ids": ids}
     raw, ids, separation = _measure(vol, m["connectivity"], m["min_voxels"], 0, m["include_background"], device, m["save_ids"], s)
-    separation = dict(settings=s, report=separation["report"], contacts=sp.contacts_table(separation["contacts"], raw["roots"], m["voxel_size"]))
+    separation = dict(settings=s, report=separation["report"], contacts=sp.contacts_table(separation["contacts"], raw["roots"], m["voxel_size"], s.get("unit")))
     return {"settings": m, "raw": raw, "table": object_table(raw, m["voxel_size"]), "ids": ids, "separation": separation}
 
 

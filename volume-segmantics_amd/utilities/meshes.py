@@ -245,7 +245,7 @@ def write_stl(path, surface: dict, voxel_size=1.0) -> Path:
 def mesh_settings(settings) -> dict:
     """the optional predict-settings keys ``mesh_surfaces``, ``mesh_values`` (a list; default None: every non-zero value present),
     ``mesh_style`` (smooth | blocky), ``mesh_format`` (ply | stl), ``mesh_triangulate`` and ``mesh_voxel_size`` (one number or [sz, sy,
-    sx]; default ``measure_voxel_size`` where that is set, else 1.0) as arguments, with ``active``: whether ``mesh_surfaces`` asks for work"""
+    sx]; default ``measure_voxel_size`` where that is set, else ``voxel_spacing``, else 1.0) as arguments, with ``active``: whether ``mesh_surfaces`` asks for work"""
     style = getattr(settings, "mesh_style", None) or "smooth"
     if style not in STYLES:
         raise ValueError(f"mesh_style {style!r}: it is one of {sorted(STYLES)}")
@@ -260,6 +260,9 @@ def mesh_settings(settings) -> dict:
     voxel_size = getattr(settings, "mesh_voxel_size", None)
     if voxel_size is None:
         voxel_size = getattr(settings, "measure_voxel_size", None)
+    grid = lv.spacing_settings(settings)
+    if voxel_size is None and grid is not None:
+        voxel_size = grid[0]
     return dict(active=bool(getattr(settings, "mesh_surfaces", False)), values=values, style=style, format=fmt,
                 triangulate=bool(getattr(settings, "mesh_triangulate", False)), voxel_size=list(lv.voxel_size(1.0 if voxel_size is None else voxel_size)))
 

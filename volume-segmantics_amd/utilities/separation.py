@@ -27,7 +27,12 @@ Routes: ``vs_separate_parents`` / ``_basins`` / ``_pair_count`` / ``_pairs`` / `
 ``vs_label_components`` on a GPU; NumPy behind ``surface_distance.squared_distance_transform`` on a host, for small volumes and for
 parity.  A value whose pair table has more than ``max_pairs`` rows is refused: that is debris, not objects.
 
-Not here: markers from the user, smoothing of the distance map, anisotropic voxels in the distance map, a watershed on image
+Anisotropic voxels (``voxel_spacing: [sz, sy, sx]``, ``spacing=``): ``R``, the peaks and the saddles are the weighted integers ``D = qz dz^2 +
+qy dy^2 + qx dx^2`` of ``label_volume.voxel_grid`` (``vs_edt_squared_scaled``; the kernels of csrc/separate.hip consume ``R`` as it comes).
+``depth`` stays in voxels of the finest axis: the merge compares ``(sqrt(H) - sqrt(S)) / w_min``, ``w_min`` the smallest weight, so an
+isotropic spacing gives the same objects bit for bit.  ``neck_radius`` is then ``unit * sqrt(neck_squared)``.
+
+Not here: markers from the user, smoothing of the distance map, a watershed on image
 intensity, separated objects in the scores of ``evaluate``, in the meshes or in the thickness report."""
 from __future__ import annotations
 
@@ -162,9 +167,11 @@ def basin_pairs(r: np.ndarray, basin: np.ndarray, connectivity: int = 6) -> dict
 
 
 # ---- the merge: shared by both routes ----------------------------------------------------------------------------------------------
-def merge_basins(peaks, peak_r, a, b, saddle, depth: float):
+def merge_basins(peaks, peak_r, a, b, saddle, depth: float, finest: int = 1):
     """(int64 array aligned with ``peaks``: the representative - the lowest peak - of every peak's merged set, the merges made).
-    ``peaks`` ascending voxel indices, ``peak_r`` their R, (``a``, ``b``, ``saddle``) the rows of the pair table."""
+    ``peaks`` ascending voxel indices, ``peak_r`` their R, (``a``, ``b``, ``saddle``) the rows of the pair table.  ``finest``: the smallest weight
+    of a weighted grid, which turns the weighted ``sqrt(H) - sqrt(S)`` into voxels of the finest axis."""
+    finest = float(finest)
     depth = _check_depth(depth)
     peaks = np.asarray(peaks, dtype=np.int64)
     position = {int(p): i for i, p in enumerate(peaks.tolist())}
@@ -183,7 +190,7 @@ def merge_basins(peaks, peak_r, a, b, saddle, depth: float):
     merges = 0
     for row in np.lexsort((b, a, -saddle)).tolist():                   # saddle descending, then A, then B
         fa, fb = find(position[int(a[row])]), find(position[int(b[row])])
-        if fa != fb and math.sqrt(float(min(height[fa], height[fb]))) - math.sqrt(float(saddle[row])) < depth:
+        if fa != fb and (math.sqrt(float(min(height[fa], height[fb]))) - math.sqrt(float(saddle[row]))) / finest < depth:
             lo, hi = min(fa, fb), max(fa, fb)                            # peaks ascend with their position: the lowest peak stays the root
             link[hi] = lo
             height[lo] = max(height[fa], height[fb])
@@ -220,18 +227,20 @@ def _not_separated(components: int, why: str) -> dict:
 
 
 # ---- host route ------------------------------------------------------------------------------------------------------------------
-def _value_host(v: np.ndarray, value: int, connectivity: int, depth: float, max_pairs, objects: np.ndarray, components: int):
+def _value_host(v: np.ndarray, value: int, connectivity: int, depth: float, max_pairs, objects: np.ndarray, components: int, weights=lv.UNIT_WEIGHTS):
     member = v == value
     if not member.any():
         return _not_separated(0, "the volume does not hold the value"), _no_contacts()
     if member.all():
         return _not_separated(components, "the volume holds no other value: there is no distance map"), _no_contacts()
-    r = np.where(member, sd.squared_distance_transform(~member, device="cpu").reshape(v.shape), 0).astype(np.uint32)
+    unit = tuple(weights) == lv.UNIT_WEIGHTS
+    r = sd.squared_distance_transform(~member, device="cpu").reshape(v.shape) if unit else sd.edt_host(~member, weights)
+    r = np.where(member, r, 0).astype(np.uint32)
     basin = basins(ascent_parents(r, connectivity)).reshape(-1)
     table = basin_pairs(r, basin.reshape(v.shape), connectivity)
     _check_pairs(len(table["a"]), max_pairs, value)
     peaks = np.flatnonzero(basin == np.arange(basin.size))
-    rep, merges = merge_basins(peaks, r.reshape(-1)[peaks], table["a"], table["b"], table["saddle"], depth)
+    rep, merges = merge_basins(peaks, r.reshape(-1)[peaks], table["a"], table["b"], table["saddle"], depth, min(weights))
     set_of_peak = np.full(basin.size, -1, dtype=np.int64)
     set_of_peak[peaks] = rep
     inside = np.flatnonzero(basin >= 0)
@@ -250,14 +259,14 @@ def _components_per_value(flat_v, flat_comp) -> np.ndarray:
     return np.bincount(flat_v[roots], minlength=256)
 
 
-def _separate_host(v: np.ndarray, values, connectivity: int, depth: float, max_pairs):
+def _separate_host(v: np.ndarray, values, connectivity: int, depth: float, max_pairs, weights=lv.UNIT_WEIGHTS):
     comp = co.label_components(v, connectivity, device="cpu")
     objects = comp.reshape(-1).astype(np.int32).copy()
     per_value = _components_per_value(v.reshape(-1), objects)
     values = _check_values(values, np.unique(v))
     report, contacts = {}, []
     for value in values:
-        report[str(value)], c = _value_host(v, value, connectivity, depth, max_pairs, objects, int(per_value[value]))
+        report[str(value)], c = _value_host(v, value, connectivity, depth, max_pairs, objects, int(per_value[value]), weights)
         contacts.append(c)
     return objects, report, _join_contacts(contacts)
 
@@ -325,7 +334,7 @@ def relabel_device(basin, set_of_peak, zyx, objects):
     return objects
 
 
-def _value_device(v, zyx, value: int, connectivity: int, depth: float, max_pairs, objects, components: int):
+def _value_device(v, zyx, value: int, connectivity: int, depth: float, max_pairs, objects, components: int, weights=lv.UNIT_WEIGHTS):
     import torch
     from .. import _lib
     device, n = v.device, v.numel()
@@ -339,7 +348,7 @@ def _value_device(v, zyx, value: int, connectivity: int, depth: float, max_pairs
     lv.require_memory(device, n + 4 * n + edt_bytes + 4 * n + 4 * n + 4 * n, f"the distance map, the basins and the relabelling of value {value} of a {tuple(zyx)} volume")
     seeds = (~member).to(torch.uint8)
     r = torch.empty(n, dtype=torch.int32, device=device)
-    sd.edt_device(seeds, zyx, r, torch.empty(edt_bytes, dtype=torch.uint8, device=device))
+    sd.edt_device(seeds, zyx, r, torch.empty(edt_bytes, dtype=torch.uint8, device=device), weights)
     del seeds                                                          # r is 0 at the seeds: off the value
     basin = basins_device(parents_device(r, zyx, connectivity), zyx)
     peaks = torch.nonzero(basin == torch.arange(n, dtype=torch.int32, device=device)).reshape(-1)      # ascending
@@ -350,7 +359,7 @@ def _value_device(v, zyx, value: int, connectivity: int, depth: float, max_pairs
     _check_pairs(len(table["a"]), max_pairs, value)
     peaks_host = peaks.cpu().numpy().astype(np.int64)
     peak_r = (r[peaks].cpu().numpy().astype(np.int64)) & 0xFFFFFFFF
-    rep, merges = merge_basins(peaks_host, peak_r, table["a"], table["b"], table["saddle"], depth)
+    rep, merges = merge_basins(peaks_host, peak_r, table["a"], table["b"], table["saddle"], depth, min(weights))
     set_of_peak = torch.full((n,), -1, dtype=torch.int32, device=device)
     set_of_peak[peaks] = torch.from_numpy(rep.astype(np.int32)).to(device)
     relabel_device(basin, set_of_peak, zyx, objects)
@@ -362,7 +371,7 @@ def _value_device(v, zyx, value: int, connectivity: int, depth: float, max_pairs
     return report, contacts
 
 
-def separate_device(v, zyx, values, connectivity: int, depth: float, max_pairs):
+def separate_device(v, zyx, values, connectivity: int, depth: float, max_pairs, weights=lv.UNIT_WEIGHTS):
     """(objects: n int32 on the device, report, contacts) from flat aligned uint8 device memory"""
     import torch
     n = v.numel()
@@ -372,28 +381,33 @@ def separate_device(v, zyx, values, connectivity: int, depth: float, max_pairs):
     values = _check_values(values, torch.unique(v).cpu().numpy())
     report, contacts = {}, []
     for value in values:
-        report[str(value)], c = _value_device(v, zyx, value, connectivity, depth, max_pairs, objects, int(per_value[value]))
+        report[str(value)], c = _value_device(v, zyx, value, connectivity, depth, max_pairs, objects, int(per_value[value]), weights)
         contacts.append(c)
     return objects, report, _join_contacts(contacts)
 
 
 # ---- public ------------------------------------------------------------------------------------------------------------------------
-def separate_prepared(v, zyx, device, values, connectivity: int, depth: float, max_pairs):
-    """``separate_objects`` on what ``components.prepare`` returned: objects flat, on the host or on the device"""
+def separate_prepared(v, zyx, device, values, connectivity: int, depth: float, max_pairs, weights=lv.UNIT_WEIGHTS):
+    """``separate_objects`` on what ``components.prepare`` returned: objects flat, on the host or on the device; ``weights``: the integer
+    weights of the axes in the distance map"""
     depth = _check_depth(depth)
+    weights = lv.check_weights(weights, zyx)
     if device is None:
-        return _separate_host(v, values, int(connectivity), depth, max_pairs)
-    return separate_device(v, zyx, values, int(connectivity), depth, max_pairs)
+        return _separate_host(v, values, int(connectivity), depth, max_pairs, weights)
+    return separate_device(v, zyx, values, int(connectivity), depth, max_pairs, weights)
 
 
-def separate_objects(vol, values=None, connectivity: int = 6, depth: float = DEFAULT_DEPTH, max_pairs=DEFAULT_MAX_PAIRS, device=None) -> dict:
+def separate_objects(vol, values=None, connectivity: int = 6, depth: float = DEFAULT_DEPTH, max_pairs=DEFAULT_MAX_PAIRS, device=None,
+                     spacing=None) -> dict:
     """``{"objects", "report", "contacts"}``: ``objects`` is an int32 array of ``vol.shape`` - for every voxel of a separated value the
     lowest voxel index of its object, for every other voxel the root of its component; ``report[str(value)]`` holds ``components``,
     ``separated`` (and ``why`` not), ``basins``, ``pair_rows``, ``adjacent_pairs``, ``merges`` and ``objects``; ``contacts`` holds, per pair of
     touching objects of one value, ``root_a < root_b`` (their ids in ``objects``), ``value``, ``faces`` (z, y, x) and ``neck_squared``, as
-    int64 arrays sorted by value, then by the pair.  ``values``: the values to separate (default: every non-zero value present)."""
+    int64 arrays sorted by value, then by the pair.  ``values``: the values to separate (default: every non-zero value present).
+    ``spacing`` [sz, sy, sx]: the distance map is that of the weighted grid (``neck_squared`` in its integers ``D``), ``depth`` in voxels of
+    the finest axis."""
     shape, zyx, device, v = co.prepare(vol, connectivity, device)
-    objects, report, contacts = separate_prepared(v, zyx, device, values, connectivity, depth, max_pairs)
+    objects, report, contacts = separate_prepared(v, zyx, device, values, connectivity, depth, max_pairs, lv.grid_of(spacing, zyx)[0])
     objects = objects.cpu().numpy() if lv.is_tensor(objects) else objects
     return {"objects": objects.astype(np.int32, copy=False).reshape(shape), "report": report, "contacts": contacts}
 
@@ -402,7 +416,9 @@ def separate_objects(vol, values=None, connectivity: int = 6, depth: float = DEF
 def separation_settings(settings) -> dict:
     """the optional predict-settings keys ``measure_separate``, ``measure_separate_values`` (a value or a list; default: every non-zero
     value present), ``measure_separate_depth`` (unit voxels, default 1.0; granular data with rough surfaces usually wants 1 to 2) and
-    ``measure_separate_max_pairs`` as arguments, with ``active``: whether ``measure_separate`` asks for work"""
+    ``measure_separate_max_pairs`` as arguments, with ``active``: whether ``measure_separate`` asks for work.  Under ``voxel_spacing`` the
+    distance map is that of the weighted grid and the result also carries ``voxel_spacing``, ``weights`` and ``unit``; the depth stays in
+    voxels of the finest axis."""
     values = getattr(settings, "measure_separate_values", None)
     if values is not None:
         values = _check_values(values, ())
@@ -412,13 +428,18 @@ def separation_settings(settings) -> dict:
     max_pairs = DEFAULT_MAX_PAIRS if max_pairs is None else int(max_pairs)
     if max_pairs < 1:
         raise ValueError("measure_separate_max_pairs must be at least 1")
-    return dict(active=bool(getattr(settings, "measure_separate", False)), values=values, depth=depth, max_pairs=max_pairs)
+    out = dict(active=bool(getattr(settings, "measure_separate", False)), values=values, depth=depth, max_pairs=max_pairs)
+    grid = lv.spacing_settings(settings)
+    if grid is not None:
+        out.update(voxel_spacing=list(grid[0]), weights=list(grid[1]), unit=grid[2])
+    return out
 
 
-def contacts_table(contacts: dict, roots, voxel_size=1.0) -> dict:
+def contacts_table(contacts: dict, roots, voxel_size=1.0, unit=None) -> dict:
     """The contacts as the columns of ``CONTACT_COLUMNS``: ``id_a`` / ``id_b`` are the ids of the object table whose rows have the roots
     ``roots`` (row + 1; 0 for an object the table does not list), ``contact_area`` = the faces across each axis x the area of a face across
-    that axis (``voxel_size``: a scalar or [sz, sy, sx]), ``neck_radius`` = sqrt(``neck_squared``) in voxels.  The coordination number of
+    that axis (``voxel_size``: a scalar or [sz, sy, sx]), ``neck_radius`` = sqrt(``neck_squared``) in voxels - under ``voxel_spacing``, with
+    ``unit`` the unit of its grid, ``unit * sqrt(neck_squared)`` in the spacing's units.  The coordination number of
     an object is the number of rows that name it."""
     sz, sy, sx = lv.voxel_size(voxel_size)
     roots = np.asarray(roots, dtype=np.int64)
@@ -435,7 +456,7 @@ def contacts_table(contacts: dict, roots, voxel_size=1.0) -> dict:
     return {"id_a": ids(np.asarray(contacts["root_a"], dtype=np.int64)), "id_b": ids(np.asarray(contacts["root_b"], dtype=np.int64)),
             "value": np.asarray(contacts["value"], dtype=np.int64), "faces_z": faces[:, 0], "faces_y": faces[:, 1], "faces_x": faces[:, 2],
             "contact_area": faces[:, 0] * (sy * sx) + faces[:, 1] * (sz * sx) + faces[:, 2] * (sz * sy), "neck_squared": neck,
-            "neck_radius": np.sqrt(neck.astype(np.float64))}
+            "neck_radius": np.sqrt(neck.astype(np.float64)) if unit is None else float(unit) * np.sqrt(neck.astype(np.float64))}
 
 
 def separation_text(report: dict) -> str:
@@ -460,7 +481,10 @@ def write_contacts(stem, table: dict, settings: dict | None = None, report: dict
         for row in rows:
             w.writerow([repr(x) if isinstance(x, float) else x for x in row])
     with open(written[1], "w") as f:
-        json.dump({"settings": json_settings(settings), "report": report, "columns": list(CONTACT_COLUMNS), "contacts": rows}, f, indent=1)
+        doc = {"settings": json_settings(settings), "report": report, "columns": list(CONTACT_COLUMNS), "contacts": rows}
+        if settings is not None and "unit" in settings:
+            doc["neck_radius"] = "unit * sqrt(neck_squared), in the units of voxel_spacing; neck_squared in the weighted integers of the grid"
+        json.dump(doc, f, indent=1)
     return written
 
 

@@ -1,7 +1,9 @@
 """Surface-distance scores of a predicted label volume against a labelled one: Hausdorff distance (maximum and 95th percentile),
 average symmetric surface distance and surface Dice at a tolerance, per class.
 
-Definitions (unit voxels; ``voxel_size`` scales distances afterwards).  For class ``c``, ``A`` is the set of voxels whose truth
+Definitions (unit voxels; ``voxel_size`` scales distances afterwards; under ``voxel_spacing: [sz, sy, sx]`` the squared distance is
+the integer ``D = qz dz^2 + qy dy^2 + qx dx^2`` of ``label_volume.voxel_grid``, the histograms are indexed by ``D`` and a distance is
+``unit * sqrt(D)`` - the surfaces do not depend on the spacing).  For class ``c``, ``A`` is the set of voxels whose truth
 class is ``c`` and ``B`` the set whose predicted class is ``c``; a voxel whose truth is the ignore label is in neither.  The surface
 ``S(M)`` is every voxel of ``M`` with one of its six face neighbours not in ``M`` - a neighbour outside the volume is not in ``M``, an
 axis of length 1 has no neighbours.  ``d2(v, S)`` is the squared Euclidean distance from ``v`` to the nearest voxel of ``S``, a uint32,
@@ -54,19 +56,23 @@ def _surface_host(mask: np.ndarray) -> np.ndarray:
     return m & ~interior
 
 
-def _minplus_axis(f: np.ndarray, axis: int) -> np.ndarray:
-    """out(p) = min over p' of f(p') + (p - p')^2 along one axis, int64 with a large mark for "none" """
+MAX_BINS = 1 << 28            # the longest histogram taken under voxel_spacing, where the bins follow the values present
+
+
+def _minplus_axis(f: np.ndarray, axis: int, q: int = 1) -> np.ndarray:
+    """out(p) = min over p' of f(p') + q (p - p')^2 along one axis, int64 with a large mark for "none" """
     f = np.moveaxis(f, axis, 0)
     length = f.shape[0]
     out = np.empty_like(f)
     pos = np.arange(length, dtype=np.int64)
     shape = (length,) + (1,) * (f.ndim - 1)
     for p in range(length):
-        out[p] = (f + ((pos - p) ** 2).reshape(shape)).min(axis=0)
+        out[p] = (f + (q * (pos - p) ** 2).reshape(shape)).min(axis=0)
     return np.moveaxis(out, 0, axis)
 
 
-def _edt_host(seeds: np.ndarray) -> np.ndarray:
+def edt_host(seeds: np.ndarray, weights=lv.UNIT_WEIGHTS) -> np.ndarray:
+    """the squared distances of a (Z, Y, X) volume; under ``weights`` the integers qz dz^2 + qy dy^2 + qx dx^2, q = w^2"""
     s = np.asarray(seeds) != 0
     if not s.any():
         return np.full(s.shape, INF_D2, dtype=np.uint32)
@@ -75,11 +81,13 @@ def _edt_host(seeds: np.ndarray) -> np.ndarray:
     except ImportError:
         ndimage = None
     if ndimage is not None:
-        return np.rint(ndimage.distance_transform_edt(~s) ** 2).astype(np.uint32)
+        if tuple(weights) == lv.UNIT_WEIGHTS:
+            return np.rint(ndimage.distance_transform_edt(~s) ** 2).astype(np.uint32)
+        return np.rint(ndimage.distance_transform_edt(~s, sampling=[float(w) for w in weights[3 - s.ndim:]]) ** 2).astype(np.uint32)
     big = np.int64(1) << 40
     d = np.where(s, np.int64(0), big)
     for axis in range(s.ndim - 1, -1, -1):
-        d = _minplus_axis(d, axis)
+        d = _minplus_axis(d, axis, int(weights[3 - s.ndim + axis]) ** 2)
     return d.astype(np.uint32)
 
 
@@ -89,12 +97,16 @@ def _histogram_host(surface: np.ndarray, d2: np.ndarray, bins: int) -> np.ndarra
 
 
 # ---- device routes ---------------------------------------------------------------------------------------------------------------
-def edt_device(seeds_dev, zyx, d2_dev, workspace):
+def edt_device(seeds_dev, zyx, d2_dev, workspace, weights=lv.UNIT_WEIGHTS):
     """vs_edt_squared on resident memory: ``seeds_dev`` n aligned uint8, ``d2_dev`` n int32 (uint32 bits), ``workspace`` a uint8 tensor of
-    ``vs_edt_workspace_bytes`` bytes (empty where none is needed)"""
+    ``vs_edt_workspace_bytes`` bytes (empty where none is needed); vs_edt_squared_scaled under ``weights`` other than (1, 1, 1)"""
     import torch
     from .. import _lib
     with torch.cuda.device(seeds_dev.device):
+        if tuple(weights) != lv.UNIT_WEIGHTS:
+            _lib.check(_lib.lib.vs_edt_squared_scaled(_lib.ptr(seeds_dev), *zyx, *(int(w) for w in weights), _lib.ptr(d2_dev),
+                                                      _lib.ptr(workspace) if workspace.numel() else None, workspace.numel(), _lib.stream_ptr()))
+            return
         _lib.check(_lib.lib.vs_edt_squared(_lib.ptr(seeds_dev), *zyx, _lib.ptr(d2_dev), _lib.ptr(workspace) if workspace.numel() else None,
                                            workspace.numel(), _lib.stream_ptr()))
 
@@ -114,16 +126,19 @@ def _surface_device(labels_dev, lut_dev, cls, zyx, out_dev, count_dev=None):
 
 
 # ---- public: the pieces ------------------------------------------------------------------------------------------------------------
-def squared_distance_transform(seeds, device=None) -> np.ndarray:
+def squared_distance_transform(seeds, device=None, spacing=None) -> np.ndarray:
     """uint32 array of ``seeds.shape``: the exact squared Euclidean distance (unit voxels) from every voxel to the nearest non-zero
-    voxel of ``seeds`` (a host array or a device tensor of one to three dimensions); 0xFFFFFFFF everywhere when there is none."""
+    voxel of ``seeds`` (a host array or a device tensor of one to three dimensions); 0xFFFFFFFF everywhere when there is none.
+    ``spacing`` [sz, sy, sx] (the steps of the LAST three axes; default: unit voxels): the integers ``D = qz dz^2 + qy dy^2 + qx dx^2`` of
+    ``label_volume.voxel_grid(spacing)``, so that a physical distance is ``unit * sqrt(D)``."""
     import torch
     shape = tuple(seeds.shape)
     zyx = _zyx(shape)
     histogram_bins(shape)        # raises when a squared distance would not fit
+    weights, _ = lv.grid_of(spacing, zyx)
     device = lv.pick_device(device, seeds)
     if device is None:
-        return _edt_host(lv.to_host(seeds)).reshape(shape)
+        return edt_host(lv.to_host(seeds).reshape(zyx), weights).reshape(shape)
     n = int(np.prod(zyx))
     from .. import _lib
     lv.require_memory(device, 5 * n + int(_lib.lib.vs_edt_workspace_bytes(*zyx)), f"the distance transform of a {shape} volume")
@@ -132,7 +147,7 @@ def squared_distance_transform(seeds, device=None) -> np.ndarray:
         s = (s != 0).to(torch.uint8)
     s = lv.aligned_u8(s, device)
     d2 = torch.empty(n, dtype=torch.int32, device=device)
-    edt_device(s, zyx, d2, _workspace(zyx, device))
+    edt_device(s, zyx, d2, _workspace(zyx, device), weights)
     return d2.cpu().numpy().view(np.uint32).reshape(shape)
 
 
@@ -157,27 +172,53 @@ def label_surface(labels, cls: int, *, label_values=None, ignore_label=None, dev
     return out.cpu().numpy().reshape(shape)
 
 
-def surface_distance_histograms(pred, truth, classes, *, label_values=None, ignore_label=None, device=None):
+def bins_present(largest: int) -> int:
+    """the bins of a histogram under voxel_spacing: the largest finite value at the masked voxels, then its own bin, then the bin of
+    the 0xFFFFFFFF voxels - not the bound of the shape, which the weights raise by up to 4096"""
+    bins = int(largest) + 2
+    if bins > MAX_BINS:
+        raise ValueError(f"a histogram of {bins} bins: under voxel_spacing a histogram holds at most 2^28 = {MAX_BINS} - use a spacing with smaller "
+                         f"integer weights")
+    return bins
+
+
+def _bins_host(surface: np.ndarray, d2: np.ndarray) -> int:
+    at = d2[surface != 0]
+    return bins_present(at[at != INF_D2].max() if (at != INF_D2).any() else 0)
+
+
+def masked_max_device(mask, d2) -> int:
+    """the largest value below 0xFFFFFFFF of ``d2`` (n int32, uint32 bits) at the voxels where ``mask`` (n uint8) is set; 0 where none"""
+    import torch
+    values = torch.where((mask != 0) & (d2 != -1), d2.to(torch.int64) & 0xFFFFFFFF, torch.zeros((), dtype=torch.int64, device=d2.device))
+    return int(values.max())
+
+
+def surface_distance_histograms(pred, truth, classes, *, label_values=None, ignore_label=None, device=None, spacing=None):
     """(hists, inf_counts) of a predicted label volume against ground truth of the same shape.
 
     ``classes``: the class count K (classes 0..K-1) or a sequence of class indices.  hists: int64 (K, 2, bins) - ``hists[i, 0, k]`` is
     the number of truth-surface voxels of class i at squared distance k from the predicted surface of that class, ``hists[i, 1, k]``
     the other way round - with the trailing bins that are zero everywhere trimmed.  inf_counts: int64 (K, 2), the surface voxels
     whose other surface is empty (d2 = 0xFFFFFFFF).  Truth values map to classes as in ``confusion_matrix``; the prediction holds
-    class indices.  On a GPU the kernels run one class and one direction at a time over two masks, one d2 volume and the workspace."""
+    class indices.  On a GPU the kernels run one class and one direction at a time over two masks, one d2 volume and the workspace.
+    ``spacing`` [sz, sy, sx]: the histograms are indexed by ``D`` of ``label_volume.voxel_grid(spacing)`` - a distance is ``unit * sqrt(D)``;
+    the surfaces themselves do not depend on it."""
     if tuple(pred.shape) != tuple(truth.shape):
         raise ValueError(f"prediction shape {tuple(pred.shape)} and ground-truth shape {tuple(truth.shape)} differ")
     shape = tuple(pred.shape)
     zyx = _zyx(shape)
     n = int(np.prod(zyx))
-    bins = histogram_bins(shape)
+    weights, _ = lv.grid_of(spacing, zyx)
+    scaled = weights != lv.UNIT_WEIGHTS
+    bins = histogram_bins(shape)       # unit voxels: every squared distance of the shape has a bin; scaled: the bins follow the values present
     class_list = list(range(int(classes))) if np.isscalar(classes) else [int(c) for c in classes]
     if not class_list or min(class_list) < 0 or max(class_list) > 253:
         raise ValueError(f"classes must be 0..253, got {class_list[:20]}")
     t, lut = ev.class_bytes(truth, label_values, ignore_label)
     p = lv.lenient_u8(pred)
     device = lv.pick_device(device, pred, truth)
-    full = np.zeros((len(class_list), 2, bins), dtype=np.int64)
+    full = {} if scaled else np.zeros((len(class_list), 2, bins), dtype=np.int64)     # scaled: (class, direction) -> its own bins
 
     if device is None:
         tc = lut[np.ascontiguousarray(lv.to_host(t))].reshape(zyx)
@@ -186,14 +227,16 @@ def surface_distance_histograms(pred, truth, classes, *, label_values=None, igno
         for i, c in enumerate(class_list):
             sa, sb = _surface_host(tc == c), _surface_host((ph == c) & ~ignored)
             if sa.any():
-                full[i, 0] = _histogram_host(sa, _edt_host(sb), bins)
+                d2 = edt_host(sb, weights)
+                full[i, 0] = _histogram_host(sa, d2, _bins_host(sa, d2) if scaled else bins)
             if sb.any():
-                full[i, 1] = _histogram_host(sb, _edt_host(sa), bins)
+                d2 = edt_host(sa, weights)
+                full[i, 1] = _histogram_host(sb, d2, _bins_host(sb, d2) if scaled else bins)
     else:
         import torch
         from .. import _lib
         work = int(_lib.lib.vs_edt_workspace_bytes(*zyx))
-        need = 2 * n + 4 * n + work + 8 * bins + (2 * n if ignore_label is not None else 0)
+        need = 2 * n + 4 * n + work + (10 * n if scaled else 8 * bins) + (2 * n if ignore_label is not None else 0)
         need += sum(n for x in (t, p) if not lv.is_resident(x, device))
         lv.require_memory(device, need, f"surface distances of a {shape} volume")
         td, pd = lv.aligned_u8(t, device), lv.aligned_u8(p, device)
@@ -205,19 +248,30 @@ def surface_distance_histograms(pred, truth, classes, *, label_values=None, igno
         masks = [torch.empty(n, dtype=torch.uint8, device=device) for _ in range(2)]
         d2 = torch.empty(n, dtype=torch.int32, device=device)
         workspace = torch.empty(work, dtype=torch.uint8, device=device)
-        hist = torch.empty(bins, dtype=torch.int64, device=device)
+        hist = None if scaled else torch.empty(bins, dtype=torch.int64, device=device)
         counts = torch.empty(2, dtype=torch.int64, device=device)
         with torch.cuda.device(device):
             for i, c in enumerate(class_list):
                 _surface_device(td, lut_dev, c, zyx, masks[0], counts[0:1])
                 _surface_device(pd, None, c, zyx, masks[1], counts[1:2])
                 for direction in range(2):
-                    edt_device(masks[1 - direction], zyx, d2, workspace)
+                    edt_device(masks[1 - direction], zyx, d2, workspace, weights)
+                    if scaled:
+                        bins = bins_present(masked_max_device(masks[direction], d2))
+                        hist = torch.empty(bins, dtype=torch.int64, device=device)
                     _lib.check(_lib.lib.vs_surface_distance_histogram(_lib.ptr(masks[direction]), _lib.ptr(d2), n, bins, _lib.ptr(hist),
                                                                       _lib.stream_ptr()))
                     full[i, direction] = hist.cpu().numpy()
-                if full[i].sum(1).tolist() != counts.cpu().tolist():
-                    raise RuntimeError(f"class {c}: the histograms hold {full[i].sum(1).tolist()} voxels, the surfaces {counts.cpu().tolist()}")
+                held = [int(full[i, direction].sum()) for direction in range(2)]
+                if held != counts.cpu().tolist():
+                    raise RuntimeError(f"class {c}: the histograms hold {held} voxels, the surfaces {counts.cpu().tolist()}")
+    if scaled:                  # to one array: the finite bins from the front, every histogram's last bin - its 0xFFFFFFFF voxels - into the last
+        bins = max([len(h) for h in full.values()] + [2])
+        padded = np.zeros((len(class_list), 2, bins), dtype=np.int64)
+        for at, h in full.items():
+            padded[at][:len(h) - 1] = h[:-1]
+            padded[at][bins - 1] = h[-1]
+        full = padded
     inf_counts = full[:, :, bins - 1].copy()
     finite = full[:, :, :bins - 1]
     used = np.flatnonzero(finite.any(axis=(0, 1)))
@@ -319,10 +373,11 @@ def surface_score_table(scores: SurfaceScores, label_values=None) -> str:
     return "\n".join(lines)
 
 
-def write_surface_scores(stem, scores: SurfaceScores, hists, inf_counts, label_values=None) -> list[Path]:
+def write_surface_scores(stem, scores: SurfaceScores, hists, inf_counts, label_values=None, grid=None) -> list[Path]:
     """``<stem>_surface_scores.csv`` (one row per class, then a ``mean`` row) and ``<stem>_surface_scores.json`` (the same figures, the
     tolerance and the voxel size, and per class the non-zero part of both histograms as squared distances and counts; NaN is
-    written as null, infinity as the string "inf")."""
+    written as null, infinity as the string "inf").  ``grid`` (``label_volume.spacing_settings``): the histograms are indexed by the
+    weighted squared distance ``D``, every figure is ``unit * sqrt(D)``, and the JSON gains ``voxel_spacing``, ``weights`` and ``unit``."""
     stem = str(stem)
     k = scores.classes
     h, inf = np.asarray(hists), np.asarray(inf_counts)
@@ -350,13 +405,19 @@ def write_surface_scores(stem, scores: SurfaceScores, hists, inf_counts, label_v
     doc = {"classes": per_class, "surface_tolerance": scores.tolerance, "voxel_size": scores.voxel_size,
            "mean_hausdorff": lv.json_number(scores.mean_hausdorff), "mean_hausdorff_95": lv.json_number(scores.mean_hausdorff_95),
            "mean_assd": lv.json_number(scores.mean_assd), "mean_surface_dice": lv.json_number(scores.mean_surface_dice)}
+    if grid is not None:
+        doc.update(voxel_spacing=list(grid[0]), weights=list(grid[1]), unit=grid[2])
     with open(written[1], "w") as f:
         json.dump(doc, f, indent=1)
     return written
 
 
 def surface_settings(settings):
-    """(enabled, tolerance, voxel size) of the optional predict-settings keys"""
+    """(enabled, tolerance, voxel size) of the optional predict-settings keys; under ``voxel_spacing`` (an error beside
+    ``evaluation_voxel_size``) the tolerance is in the spacing's units and the voxel size is the grid's unit"""
+    grid = lv.spacing_settings(settings, "evaluation_voxel_size")
+    if grid is not None:
+        return bool(getattr(settings, "evaluation_surface_distances", False)), float(getattr(settings, "evaluation_surface_tolerance", 1.0)), grid[2]
     return (bool(getattr(settings, "evaluation_surface_distances", False)), float(getattr(settings, "evaluation_surface_tolerance", 1.0)),
             float(getattr(settings, "evaluation_voxel_size", 1.0)))
 
@@ -366,9 +427,11 @@ def evaluate_surface_distances(pred, truth, classes: int, settings, *, label_val
     table in the log and, with ``stem``, the two files.  Returns (scores, hists, inf_counts)."""
     import logging
     _, tolerance, voxel_size = surface_settings(settings)
-    hists, inf_counts = surface_distance_histograms(pred, truth, classes, label_values=label_values, ignore_label=ignore_label, device=device)
+    grid = lv.spacing_settings(settings, "evaluation_voxel_size")
+    hists, inf_counts = surface_distance_histograms(pred, truth, classes, label_values=label_values, ignore_label=ignore_label, device=device,
+                                                    spacing=None if grid is None else grid[0])
     scores = surface_scores_from_histograms(hists, inf_counts, tolerance, voxel_size)
     logging.info("Surface distances against the label volume:\n" + surface_score_table(scores, label_values))
     if stem is not None:
-        write_surface_scores(stem, scores, hists, inf_counts, label_values)
+        write_surface_scores(stem, scores, hists, inf_counts, label_values, grid)
     return scores, hists, inf_counts
